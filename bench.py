@@ -19,9 +19,12 @@ gradient exchange over the DP group (RCCL reduce-scatter, ZeRO-2 style sharded o
 `--no-zero2`), global-norm clipping at 1.0 and the fused AdamW (+ in-place all-gather of the bf16 weights).
 Synthetic data of the real shape (336x336 image -> 576 patches + 1472 text tokens = 2048 context, 512 response
 tokens; `--ragged`: text lengths U[600,1473]), random init of the real architecture.  value = image-text
-samples / s over ALL ranks (weak scaling: fixed work per GPU).  Prints ONE JSON line on rank 0 with `roofline`
-(dominant kernel, timed live with HIP events) and `cpu_baseline` (the fp32 oracle's full-depth step on the host cores,
-rank 0 at N=1, with the GPU-vs-oracle loss difference).
+samples / s over ALL ranks (weak scaling: fixed work per GPU).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line.  `--full` adds what takes runs of its own:
+`roofline` (dominant kernel, timed live with HIP events; the in-step kernel aggregate), `optimizer_ms`, the config-4 / config-5
+legs under `extra` and `cpu_baseline` (the fp32 oracle's full-depth step on the host cores, rank 0 at N=1, with the
+GPU-vs-oracle loss difference).  `--dump-outputs DIR` writes what the last timed step computed as .npy files (`dump_outputs`).
 """
 import argparse
 import json
@@ -838,6 +841,28 @@ def _floor_entry(g, c, tw_forced, tw_free):
     return e
 
 
+def dump_outputs(out_dir, trainer, opt, accum, n_sample=1 << 20):
+    """`--dump-outputs DIR`: what the last timed optimizer step handed its caller, as float32 .npy files in DIR (about 12 MB), so
+    that two builds can be compared output for output on the same seeded inputs.  The logged scalars of each of the step's
+    `accum` micro-batches (`loss`, `loss/align`, ... -> loss.npy, loss_align.npy, ...), the norm of the mean gradient the
+    clipping saw, and this rank's updated AdamW state (fp32 master weights, first and second moments) at `n_sample` positions
+    drawn from a fixed seed: the same positions in every run of the same configuration."""
+    import numpy as np
+    opt.sync()
+    torch.cuda.synchronize()
+    arrays = {k.replace("/", "_"): torch.stack([t.float().reshape(()) for t in v[-accum:]])
+              for k, v in trainer._stored_metrics["train"].items()}
+    if opt.max_grad_norm:
+        arrays["grad_norm"] = opt.grad_norm
+    idx = torch.randint(0, opt.n_state, (min(n_sample, opt.n_state),), generator=torch.Generator().manual_seed(0))
+    idx = idx.sort().values.to(opt.master.device)
+    for name, t in (("master_sample", opt.master), ("adam_m_sample", opt.m), ("adam_v_sample", opt.v)):
+        arrays[name] = t[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def _free_port():
     import socket
     sk = socket.socket()
@@ -943,9 +968,15 @@ def main():
     ap.add_argument("--unpad", action="store_true",
                     help="with --ragged: unpadded (cu_seqlens) execution — no padding rows in any kernel (the MoE gate then does "
                          "not see padding rows either, unlike the reference)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the dominant kernel live (`roofline`), the in-step "
+                         "kernel aggregate, the optimizer timing, the config-4 / config-5 legs (`extra`) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (logged losses, gradient norm, a seeded sample of the updated "
+                         "optimizer state) as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the short config-4 (DPO) and config-5 (8-expert student) legs appended under `extra` at N=1")
+                    help="--full without the short config-4 (DPO) and config-5 (8-expert student) legs appended under `extra` at N=1")
     ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "full", "sample"],
                     help="auto: full-depth oracle step (same weights, loss compared with the GPU) when host RAM >= 96 GB")
     ap.add_argument("--twin-device", default="cuda", choices=["cuda", "cpu", "off"],
@@ -1095,17 +1126,20 @@ def main():
     dt, last = timed(step, 0, args.steps, first=args.warmup)
     comm1 = {k: list(v) for k, v in engine.COMM.items()}      # the collectives of the TIMED steps only (later legs issue more)
     loss_val = float(last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, opt, A)      # before any --full leg steps the optimizer again
 
     # Everything below that LAUNCHES work runs on EVERY rank: the in-step aggregate is one more optimizer step and the optimizer timing
     # runs the sharded AdamW with its all-gathers — at N > 1 both contain collectives, and a rank that ran them alone would wait for its
     # peers forever (rounds 4's bench did exactly that on rank 0; the N > 1 lines of round 3 predate it).  Only rank 0 reports.
     # dominant kernel = the top row of the committed rocprofv3 summary of this workload (`roofline_recipe`), at the shape it spends
     # most of its time on, measured live with HIP events on the launch stream (torch's current stream)
-    dom, dom_key, dom_label = roofline_recipe()
-    gemm_ms, dom_flops, algo_bytes, dom_shape = time_dominant_kernel(dom_key, B, dev)
-    gemm_tf = dom_flops / (gemm_ms * 1e-3) / 1e12
-    in_step = in_step_gemm_aggregate(step, args.warmup + args.steps)
-    optimizer_ms = time_optimizer(gb, opt, world * A)
+    if args.full:
+        dom, dom_key, dom_label = roofline_recipe()
+        gemm_ms, dom_flops, algo_bytes, dom_shape = time_dominant_kernel(dom_key, B, dev)
+        gemm_tf = dom_flops / (gemm_ms * 1e-3) / 1e12
+        in_step = in_step_gemm_aggregate(step, args.warmup + args.steps)
+        optimizer_ms = time_optimizer(gb, opt, world * A)
     if world > 1:
         dist.barrier()
 
@@ -1113,20 +1147,6 @@ def main():
         sps = args.steps * B * A * world / dt
         ledger = TFLOP_PER_SAMPLE_LEDGER * (2.0 if args.stage == "dpo" else 1.0)      # DPO: 105.96 TFLOP per pair
         achieved = ledger * sps / world
-        # HBM-side bytes per launch of that kernel come from the committed PMC passes (they cannot be collected live); the
-        # ALGORITHMIC bytes are those of the launch timed above (operands and result once, bf16)
-        traffic, traffic_note = None, f"no committed PMC pass for this kernel and shape; algorithmic {algo_bytes / 1e9:.2f} GB"
-        for r_ in range(20, 0, -1):
-            tp = os.path.join(ROOT, "profiles", f"r{r_:02d}_final_gemm_traffic.json")
-            if not os.path.exists(tp):
-                continue
-            tj = json.load(open(tp))
-            if tj["shape"] == dom_shape and tj["kernel"].split("<")[1][:1] == dom_label.split("<")[1][:1]:
-                traffic = round((tj["fetch_bytes_corrected"] + tj["write_bytes"]) / 1e9, 2)
-                traffic_note = (f"GB per launch at the L2/fabric boundary (Infinity-Cache hits included), {tj['source']}; "
-                                f"algorithmic (operands + result once, bf16) {algo_bytes / 1e9:.2f} GB => {traffic * 1e9 / algo_bytes:.2f}x — see "
-                                f"profiles/{os.path.basename(tp).replace('gemm_traffic.json', 'pmc.md')}")
-                break
         out = {
             "metric": "distillation samples/sec (336px img + 2k ctx), 2B-MoE student / 7B teacher",
             "value": round(sps, 4), "unit": "samples/s" if args.stage == "mimic" else "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1153,19 +1173,34 @@ def main():
                        "trainable_params": n_train, "lm_head_rows": "loss rows only (513 of 2048 per sample)",
                        "final_loss": round(loss_val, 4),
                        "peak_hbm_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)},
-            "roofline": {"bound": "mfma", "kernel": f"{dom_label} [{dom_shape[0]}x{dom_shape[1]}x{dom_shape[2]}]",
-                         "dominant_by": (f"top row of profiles/{dom['file']}: `{dom['name']}` {dom['pct']} % of GPU time; "
-                                         f"gemm4 / gemm4t family (one K loop, different epilogues) {dom['family_pct']} %") if dom else "no committed kernel summary",
-                         "achieved": round(gemm_tf, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(gemm_tf / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_note": traffic_note,
-                         "launch_ms": round(gemm_ms, 4),
-                         "achieved_note": "live micro-launch: 10 launches at this shape, HIP events on the launch stream",
-                         "in_step": in_step,
-                         "whole_step": whole_step_object(sps / world, args.stage, args.experts)},
-            "optimizer_ms": optimizer_ms,
-            "exchange": exchange_object(dp, opt, args.steps, comm0, comm1),
         }
-        want_extras = (world == 1 and not args.no_extras and args.stage == "mimic" and args.experts == 4 and not args.ragged
+        if args.full:
+            # HBM-side bytes per launch of that kernel come from the committed PMC passes (they cannot be collected live); the
+            # ALGORITHMIC bytes are those of the launch timed above (operands and result once, bf16)
+            traffic, traffic_note = None, f"no committed PMC pass for this kernel and shape; algorithmic {algo_bytes / 1e9:.2f} GB"
+            for r_ in range(20, 0, -1):
+                tp = os.path.join(ROOT, "profiles", f"r{r_:02d}_final_gemm_traffic.json")
+                if not os.path.exists(tp):
+                    continue
+                tj = json.load(open(tp))
+                if tj["shape"] == dom_shape and tj["kernel"].split("<")[1][:1] == dom_label.split("<")[1][:1]:
+                    traffic = round((tj["fetch_bytes_corrected"] + tj["write_bytes"]) / 1e9, 2)
+                    traffic_note = (f"GB per launch at the L2/fabric boundary (Infinity-Cache hits included), {tj['source']}; "
+                                    f"algorithmic (operands + result once, bf16) {algo_bytes / 1e9:.2f} GB => {traffic * 1e9 / algo_bytes:.2f}x — see "
+                                    f"profiles/{os.path.basename(tp).replace('gemm_traffic.json', 'pmc.md')}")
+                    break
+            out["roofline"] = {"bound": "mfma", "kernel": f"{dom_label} [{dom_shape[0]}x{dom_shape[1]}x{dom_shape[2]}]",
+                               "dominant_by": (f"top row of profiles/{dom['file']}: `{dom['name']}` {dom['pct']} % of GPU time; "
+                                               f"gemm4 / gemm4t family (one K loop, different epilogues) {dom['family_pct']} %") if dom else "no committed kernel summary",
+                               "achieved": round(gemm_tf, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                               "frac": round(gemm_tf / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_note": traffic_note,
+                               "launch_ms": round(gemm_ms, 4),
+                               "achieved_note": "live micro-launch: 10 launches at this shape, HIP events on the launch stream",
+                               "in_step": in_step,
+                               "whole_step": whole_step_object(sps / world, args.stage, args.experts)}
+            out["optimizer_ms"] = optimizer_ms
+        out["exchange"] = exchange_object(dp, opt, args.steps, comm0, comm1)
+        want_extras = (args.full and world == 1 and not args.no_extras and args.stage == "mimic" and args.experts == 4 and not args.ragged
                        and B == 16 and args.ep == 1)
         if want_extras:
             # config 4 on the SAME models (VERDICT r04 next #1b): the preference stage's own step — 8 pairs x accum (two student
@@ -1182,7 +1217,7 @@ def main():
                 del step4
             except Exception as e:
                 out["extra"] = {"config4_pairs_per_s": {"error": repr(e)[:300]}}
-        if world == 1 and not args.no_cpu_baseline and not args.ragged:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.ragged:
             try:
                 out["cpu_baseline"] = cpu_baseline(student, teacher, trainer, args.cpu_baseline, gb=gb, stage=args.stage, twin_device=args.twin_device,
                                                    dpo_pairs=args.dpo_pairs, forced_arm=args.cpu_forced_arm)

@@ -26,8 +26,8 @@ def _bench(extra_args, env_extra, timeout=900):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         if not env_extra.get(k):
             env.pop(k, None)              # a launcher environment of the test runner itself must not leak into the child
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--micro-batch", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-           "--no-extras"] + extra_args
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--micro-batch", "2", "--steps", "1", "--warmup", "1", "--full",
+           "--no-cpu-baseline", "--no-extras"] + extra_args
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

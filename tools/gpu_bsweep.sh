@@ -2,7 +2,7 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 mkdir -p gpurun_out/bsweep
 for b in ${1:-1 4 8 16 24}; do
-  timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --micro-batch $b 2>/dev/null | python -c "
+  timeout 600 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --micro-batch $b 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     try: r = json.loads(l)

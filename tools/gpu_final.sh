@@ -7,8 +7,8 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/${1:-final}
 mkdir -p $OUT
-timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/bench -o a --output-format csv -- python $OLDPWD/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-teacher-prefetch > $OUT/bench_trace.log 2>&1)
+timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/bench -o a --output-format csv -- python $OLDPWD/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras --no-teacher-prefetch > $OUT/bench_trace.log 2>&1)
 grep '^{' $OUT/bench_trace.log | tail -1 > $OUT/bench_line.json
 SQ1="GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT"
 # (round 6: tools/gemm_one.py launches the kernel the bench line's roofline describes — G1_KERNEL, default the fused SwiGLU forward — and says which in gemm_one_meta.json)
@@ -24,7 +24,7 @@ timeout 600 python tools/bench_kernels.py > $OUT/kernel_microbench.jsonl 2> $OUT
 timeout 300 python tools/bench_gemm.py > $OUT/gemm_shapes.json 2> $OUT/gemm_shapes.err
 timeout 300 python tools/bench_attn.py --bwd-only > $OUT/attn_bench.jsonl 2>/dev/null
 timeout 300 python tools/bench_attn.py >> $OUT/attn_bench.jsonl 2>/dev/null
-if [ -n "$FINAL_DPO" ]; then timeout 1500 python bench.py --stage dpo --micro-batch 8 > $OUT/bench_dpo.json 2> $OUT/bench_dpo.err; echo "dpo rc=$?"; fi
+if [ -n "$FINAL_DPO" ]; then timeout 1500 python bench.py --stage dpo --micro-batch 8 --full > $OUT/bench_dpo.json 2> $OUT/bench_dpo.err; echo "dpo rc=$?"; fi
 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_form.json 2>/dev/null
 timeout 300 python tools/bench_r5_routing.py > $OUT/routing.jsonl 2>/dev/null
 for ds in 1 0; do LMOD_ATTN_DS=$ds timeout 300 python tools/bench_attn.py --bwd-only 2>/dev/null | grep attn_bwd >> $OUT/attn_bwd_forms.jsonl; done

@@ -32,7 +32,7 @@ def stats_md():
     qkv_calls = sum(1 for r in trace if "gemm4_kernel<5" in r["Kernel_Name"])
     n_steps = steps_in_trace(qkv_calls, A) or (line["steps"] + line["warmup"])
     out = [f"# rocprofv3 --kernel-trace --stats of the default bench workload ({TAG})", "",
-           "Command (MI355X box): `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 3 --warmup 1 "
+           "Command (MI355X box): `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 3 --warmup 1 --full "
            "--no-cpu-baseline --no-extras --no-teacher-prefetch` (teacher pipelining off so that kernel durations do not overlap; the "
            "default bench line with pipelining on is in `*_bench_n1.json`).", "",
            f"{n_steps:g} optimizer steps in the trace ({line['warmup']} warm-up + {line['steps']} timed + the in-step-aggregate step; counted from the "
