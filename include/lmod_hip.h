@@ -246,6 +246,21 @@ int lmod_lossplan_fill(const long long* labels, int B, int S, int kd_rows, int c
 /* Greedy decoding: out[r] = argmax_v logits[r, v] over bf16 rows (first maximum wins). */
 int lmod_row_argmax_bf16(const void* logits, long long ld, int V, int* out, int R, hipStream_t stream);
 
+/* ---- beam search (generate(num_beams > 1); HF GenerationMixin._beam_search, do_sample=False) ---------------------------
+ * lmod_beam_topk_bf16: logits [B*nb, ld] bf16 (V <= ld live columns), beam_scores [B*nb] fp32 -> per sample b the top K = 2*nb of
+ *   log_softmax(logits[row]) + beam_scores[row] over its nb rows x V tokens, sorted by score descending, equal scores by the
+ *   smaller beam*V + token: out_score [B, K] fp32, out_beam [B, K] (0..nb-1), out_token [B, K].  Two launches: the rows are cut
+ *   into chunks of `chunk` tokens (a multiple of 8) that reduce to (max, sum exp, top K) in ws (ws_bytes >=
+ *   B * nb * ceil(V / chunk) * (2 + 2 * KC) * 4, KC = 2*nb rounded up to a power of two), one workgroup per sample merges them.
+ *   1 <= nb <= 8.
+ * lmod_kv_gather_rows: for every tensor t < ntensor (device tables dst[t] / src[t] of [rows, smax, width] bf16 caches, 16-byte
+ *   aligned) dst[t][r, 0:lens[r], :] = src[t][src_row[r], 0:lens[r], :], r < R, src_row[r] < R_src; positions >= lens[r] are not
+ *   touched.  width % 8 == 0.  dst and src must not overlap (a permutation is not gathered in place). */
+int lmod_beam_topk_bf16(const void* logits, long long ld, int V, const float* beam_scores, int B, int nb, int chunk, float* ws,
+                        long long ws_bytes, float* out_score, int* out_beam, int* out_token, hipStream_t stream);
+int lmod_kv_gather_rows(void* const* dst, const void* const* src, int ntensor, const int* src_row, const int* lens, int R,
+                        int R_src, int smax_dst, int smax_src, int width, hipStream_t stream);
+
 /* ---- sparse MoE (DeepSpeed 0.9.5 TopKGate/top1gating/top2gating/MOELayer semantics) ------------
  * logits[T,E] = x.float() @ wg^T  (TopKGate.forward; wg kept fp32).
  * Experts per layer: 1 <= E <= 32 (`--num_experts`, config/args.py:46); the per-token kernels are instantiated for

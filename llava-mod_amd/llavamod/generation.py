@@ -1,0 +1,147 @@
+"""Beam-search bookkeeping of `generate(num_beams > 1)` in plain torch (no kernels, importable without the HIP library).
+
+The semantics are HF `GenerationMixin._beam_search` (do_sample=False) of transformers 5.x, the version this project can run:
+  * running beam scores start as [0, -1e9, ...] per sample; a step's candidates are the top 2*nb of
+    log_softmax(logits) + beam score over nb*V per sample, sorted by score (descending);
+  * a candidate "hits" when its token is EOS, or on the last step (max_new_tokens) for every candidate;
+  * the best nb candidates that do not hit continue (their un-normalised score is the new beam score);
+  * a hitting candidate ranked below nb is dropped; one ranked within nb enters the sample's finished list (nb slots) with
+    score sum_logprobs / n_generated ** length_penalty (n_generated counts the EOS), unless the sample is closed (its early-stop
+    heuristic is satisfied, or early_stopping=True and all nb slots are full);
+  * the heuristic closes a sample once every slot is full and the best running score / n_generated ** length_penalty
+    cannot beat the worst finished score; the search ends when every sample is closed, when early_stopping=True and every
+    slot of every sample is full, or at max_new_tokens.
+Where transformers 4.37's BeamSearchScorer differs, this follows 5.x: at max_new_tokens 4.37 finalises the nb running beams
+chosen after that step (the best non-EOS candidates, even below rank nb), 5.x admits the top nb candidates of the last step
+themselves.  Length normalisation counts generated tokens only, so right padding of the prompt never changes a score.
+
+Per step the caller hands over a candidate block [B, 2*nb] (score fp32, beam in 0..nb-1, token) and gets back the next tokens
+[B*nb], the flat source rows [B*nb] (cache row b*nb + beam) and the new running beam scores [B*nb].
+"""
+import torch
+
+NEG = -1.0e9
+
+
+def check_beam_args(num_beams, num_return_sequences=1, do_sample=False, length_penalty=1.0, early_stopping=False):
+    if do_sample:
+        raise ValueError("beam sampling (do_sample=True with num_beams > 1) is not supported: use do_sample=False for beam "
+                         "search or num_beams=1 for sampling")
+    if not isinstance(num_beams, int) or not 2 <= num_beams <= 8:
+        raise ValueError(f"num_beams must be an int in 2..8 for beam search, got {num_beams!r}")
+    if not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= num_beams:
+        raise ValueError(f"num_return_sequences must be in 1..num_beams ({num_beams}), got {num_return_sequences!r}")
+    if early_stopping not in (False, True):
+        raise ValueError(f"early_stopping must be False or True, got {early_stopping!r}")
+    float(length_penalty)
+
+
+class BeamSearchScorer:
+    """Hypothesis lists, done flags and the early-stop test of a beam search over B samples x nb beams.  All state lives on
+    `device` (the host by default: the candidate block is read back once per step)."""
+
+    def __init__(self, batch_size, num_beams, max_new_tokens, length_penalty=1.0, early_stopping=False, eos_token_id=None,
+                 pad_token_id=None, device="cpu"):
+        check_beam_args(num_beams, 1, False, length_penalty, early_stopping)
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        B, nb = batch_size, num_beams
+        self.B, self.nb, self.max_new = B, nb, int(max_new_tokens)
+        self.length_penalty, self.early_stopping = float(length_penalty), early_stopping
+        self.eos = eos_token_id
+        pad = eos_token_id if pad_token_id is None else pad_token_id
+        self.pad = 0 if pad is None else int(pad)
+        self.device = device
+        i64 = dict(dtype=torch.int64, device=device)
+        self.running_seq = torch.full((B, nb, self.max_new), self.pad, **i64)
+        self.running_scores = torch.zeros((B, nb), dtype=torch.float32, device=device)
+        self.running_scores[:, 1:] = NEG
+        self.seq = torch.full((B, nb, self.max_new), self.pad, **i64)          # finished hypotheses (nb slots, best first)
+        self.scores = torch.full((B, nb), NEG, dtype=torch.float32, device=device)
+        self.lens = torch.zeros((B, nb), **i64)
+        self.finished = torch.zeros((B, nb), dtype=torch.bool, device=device)
+        self.open = torch.ones((B, 1), dtype=torch.bool, device=device)          # early-stop heuristic not yet satisfied
+        self.top_nb = torch.arange(2 * nb, device=device) < nb
+        self.t = 0                                                              # tokens generated so far
+        self.is_done = False
+
+    def initial_beam_scores(self):
+        """[B*nb] fp32: 0 for the first beam of every sample, -1e9 for the others (all beams start as the same prompt)."""
+        return self.running_scores.reshape(-1).clone()
+
+    @staticmethod
+    def _gather(x, idx):
+        return torch.gather(x, 1, idx.reshape(idx.shape + (1,) * (x.dim() - 2)).expand(idx.shape + x.shape[2:]))
+
+    def step(self, scores, beams, tokens):
+        """scores fp32 [B, 2nb] (log-prob sums, sorted descending per sample), beams / tokens int [B, 2nb].
+        Returns (next_tokens int64 [B*nb], src_rows int64 [B*nb], beam_scores fp32 [B*nb])."""
+        if self.is_done:
+            raise RuntimeError("beam search already finished")
+        B, nb, t = self.B, self.nb, self.t
+        dev = self.device
+        scores = scores.to(device=dev, dtype=torch.float32)
+        beams, tokens = beams.to(device=dev, dtype=torch.int64), tokens.to(device=dev, dtype=torch.int64)
+        assert scores.shape == (B, 2 * nb) and beams.shape == scores.shape and tokens.shape == scores.shape
+        cand_seq = self._gather(self.running_seq, beams).clone()                   # [B, 2nb, max_new]
+        cand_seq[:, :, t] = tokens
+        hits = torch.zeros_like(tokens, dtype=torch.bool)
+        if self.eos is not None:
+            hits |= tokens == int(self.eos)
+        if t + 1 >= self.max_new:
+            hits[:] = True
+        # running beams for the next step: the best nb candidates that do not hit
+        run_scores = scores + hits.to(torch.float32) * NEG
+        nxt = torch.topk(run_scores, k=nb)[1]
+        self.running_seq = self._gather(cand_seq, nxt)
+        self.running_scores = self._gather(run_scores, nxt)
+        next_tokens = self._gather(tokens, nxt)
+        src_rows = self._gather(beams, nxt) + torch.arange(B, device=dev)[:, None] * nb
+        # finished hypotheses: candidates ranked within nb that hit, length-normalised, merged with the nb slots
+        admitted = hits & self.top_nb[None, :]
+        fin = scores / ((t + 1) ** self.length_penalty)
+        full = torch.all(self.finished, dim=-1, keepdim=True) & (self.early_stopping is True)
+        fin = fin + full.to(torch.float32) * NEG
+        fin = fin + (~self.open).to(torch.float32) * NEG
+        fin = fin + (~admitted) * NEG
+        m_seq = torch.cat((self.seq, cand_seq), 1)
+        m_scores = torch.cat((self.scores, fin), 1)
+        m_lens = torch.cat((self.lens, torch.full_like(tokens, t + 1)), 1)
+        m_fin = torch.cat((self.finished, admitted), 1)
+        keep = torch.topk(m_scores, k=nb)[1]
+        self.seq, self.scores = self._gather(m_seq, keep), self._gather(m_scores, keep)
+        self.lens, self.finished = self._gather(m_lens, keep), self._gather(m_fin, keep)
+        # early-stop heuristic and the end of the search
+        self.t = t = t + 1
+        best = self.running_scores[:, :1] / (t ** self.length_penalty)
+        worst = torch.where(self.finished, torch.min(self.scores, dim=1, keepdim=True)[0], NEG)
+        self.open = self.open & torch.any(best > worst, dim=-1, keepdim=True)
+        improvement_possible = bool(torch.any(self.open))
+        open_beam = not (bool(torch.all(self.finished)) and self.early_stopping is True)
+        continuations = not bool(torch.all(hits))
+        self.is_done = not (improvement_possible and open_beam and continuations)
+        return next_tokens.reshape(-1), src_rows.reshape(-1), self.running_scores.reshape(-1).clone()
+
+    def finalize(self, num_return_sequences=1):
+        """Best `num_return_sequences` finished hypotheses per sample, best first: (tokens int64 [B*n, L], scores fp32 [B*n]),
+        L = the longest returned hypothesis; positions after a hypothesis ends hold pad_token_id (an EOS that ended it stays)."""
+        n = int(num_return_sequences)
+        if not 1 <= n <= self.nb:
+            raise ValueError(f"num_return_sequences must be in 1..{self.nb}")
+        seq = self.seq[:, :n].reshape(self.B * n, -1)
+        lens = self.lens[:, :n].reshape(-1)
+        L = max(int(lens.max()), 1)
+        return seq[:, :L].contiguous(), self.scores[:, :n].reshape(-1).clone()
+
+
+def unpack_candidates(block):
+    """The int32 block [3, B, 2nb] of kernels.beam_topk -> (scores fp32, beams, tokens), each [B, 2nb]."""
+    return block[0].view(torch.float32), block[1], block[2]
+
+
+class BeamSearchOutput:
+    """`generate(num_beams > 1, return_dict_in_generate=True)`: sequences int64 [B*n, L] (new tokens only, best first per sample)
+    and sequences_scores fp32 [B*n] (length-normalised sum of log-probabilities)."""
+
+    def __init__(self, sequences, sequences_scores):
+        self.sequences, self.sequences_scores = sequences, sequences_scores

@@ -399,6 +399,47 @@ def attn_decode(q, kcache, vcache, lens, nh, nkv, hd, scale):
     return out
 
 
+# ------------------------------------------------------------------------------------------ beam search
+def beam_topk(logits, beam_scores, nb):
+    """logits [B*nb, V] bf16 (row stride may exceed V), beam_scores [B*nb] fp32 -> one int32 block [3, B, 2*nb]: per sample the top
+    2*nb of log_softmax(logits) + beam score over nb*V, sorted descending (ties: smaller beam*V + token); row 0 holds the scores
+    (fp32 bits), row 1 the beam (0..nb-1), row 2 the token — one block, so the host reads the candidates back with one copy."""
+    R, V = logits.shape
+    assert logits.dtype == BF16 and logits.stride(1) == 1 and R % nb == 0
+    assert beam_scores.dtype == torch.float32 and beam_scores.is_contiguous() and beam_scores.numel() == R
+    B, K = R // nb, 2 * nb
+    # ~384 workgroups over all rows (4 rows alone would fill 4 of 256 CUs), chunks of at least 512 tokens
+    c_target = max(1, min(-(-384 // R), -(-V // 512)))
+    chunk = (-(-V // c_target) + 7) // 8 * 8
+    C = -(-V // chunk)
+    ws = torch.empty(R * C * (2 + 2 * 16), device=logits.device, dtype=torch.float32)
+    out = torch.empty((3, B, K), device=logits.device, dtype=torch.int32)
+    call("lmod_beam_topk_bf16", ptr(logits), logits.stride(0), V, ptr(beam_scores), B, nb, chunk, ptr(ws), ws.numel() * 4,
+         ptr(out[0]), ptr(out[1]), ptr(out[2]))
+    return out
+
+
+def ptr_table(tensors):
+    """Device table (int64) of the data pointers of `tensors` (for kv_gather_rows)."""
+    return torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64).to(tensors[0].device)
+
+
+def kv_gather_rows(dst, src, src_row, lens, tables=None):
+    """dst[t][r, :lens[r]] = src[t][src_row[r], :lens[r]] for every tensor pair (lists of contiguous [rows, smax, width] bf16
+    caches, one width), one launch; positions >= lens[r] stay as they are.  tables: (ptr_table(dst), ptr_table(src)) when the
+    caller keeps them.  dst and src must be different buffers."""
+    assert len(dst) == len(src) and len(dst) > 0
+    d0, s0 = dst[0], src[0]
+    for d, s in zip(dst, src):
+        assert d.dtype == BF16 and s.dtype == BF16 and d.is_contiguous() and s.is_contiguous()
+        assert d.shape[0] == d0.shape[0] and d.shape[1:] == d0.shape[1:] and s.shape == s0.shape and s.shape[2] == d.shape[2]
+    R = d0.shape[0]
+    assert src_row.dtype == torch.int32 and lens.dtype == torch.int32 and src_row.numel() == R and lens.numel() == R
+    dt, st = tables if tables is not None else (ptr_table(dst), ptr_table(src))
+    call("lmod_kv_gather_rows", ptr(dt), ptr(st), len(dst), ptr(src_row.contiguous()), ptr(lens.contiguous()), R, s0.shape[0],
+         d0.shape[1], s0.shape[1], d0.shape[2])
+
+
 # ------------------------------------------------------------------------------------------ MoE
 def moe_router_fwd(x, wg):
     T, H = x.shape

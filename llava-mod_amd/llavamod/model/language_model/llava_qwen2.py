@@ -264,12 +264,17 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
 
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, images=None, max_new_tokens=16, eos_token_id=None,
-                 pad_token_id=None, do_sample=False, temperature=1.0, top_k=None, top_p=None, seed=None, **kwargs):
+                 pad_token_id=None, do_sample=False, temperature=1.0, top_k=None, top_p=None, seed=None, num_beams=1,
+                 num_return_sequences=1, length_penalty=1.0, early_stopping=False, return_dict_in_generate=False, **kwargs):
         """Generation with a KV cache (the reference's eval path calls HF `generate` on the Eval model,
-        llava_qwen2_moe.py:629-681; its serving code passes do_sample / temperature / top_p).  Greedy by default; do_sample=True
-        draws from the temperature / top-k / top-p filtered distribution (`seed` makes the draw reproducible).  Right-padded
-        prompts: every sample continues from its own length.  Returns the NEW tokens [B, <= max_new_tokens] (int64; positions
-        after a sample's EOS hold pad_token_id)."""
+        llava_qwen2_moe.py:629-681; its serving code passes do_sample / temperature / top_p, its eval scripts num_beams).
+        Greedy by default; do_sample=True draws from the temperature / top-k / top-p filtered distribution (`seed` makes the
+        draw reproducible); num_beams > 1 is beam search (`_beam_generate`).  Right-padded prompts: every sample continues
+        from its own length.  Returns the NEW tokens [B, <= max_new_tokens] (int64; positions after a sample's EOS hold
+        pad_token_id)."""
+        if num_beams != 1:
+            return self._beam_generate(input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, do_sample,
+                                       num_beams, num_return_sequences, length_penalty, early_stopping, return_dict_in_generate)
         was_training = self.training
         self.eval()
         cache, logits = self._prefill(input_ids, attention_mask, images, max_new_tokens)
@@ -296,6 +301,47 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
             logits = self._decode_step(nxt, cache)
         self.train(was_training)
         return torch.stack(out, 1)
+
+    @torch.no_grad()
+    def _beam_generate(self, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, do_sample, num_beams,
+                       num_return_sequences, length_penalty, early_stopping, return_dict_in_generate):
+        """Beam search (HF `_beam_search`, do_sample=False; the bookkeeping and where it follows transformers 5.x rather than
+        4.37: llavamod/generation.py).  The prompt is prefilled once at B rows and its cache replicated into B*num_beams rows
+        (smax = S + max_new_tokens); every step is lmod_beam_topk_bf16 (top 2*nb candidates per sample, on the device) -> one
+        read-back of the candidate block -> scorer -> lmod_kv_gather_rows (the beams' parent rows into the second cache buffer)
+        -> one decode step over B*nb tokens.  Returns the new tokens [B*num_return_sequences, L] (int64, best hypothesis first
+        within each sample; an EOS that ended a hypothesis stays, later positions hold pad_token_id); with
+        return_dict_in_generate an object with `sequences` and `sequences_scores` (fp32, length-normalised)."""
+        from ...generation import BeamSearchOutput, BeamSearchScorer, check_beam_args, unpack_candidates
+        check_beam_args(num_beams, num_return_sequences, do_sample, length_penalty, early_stopping)
+        was_training = self.training
+        self.eval()                            # the MoE student routes with eval_capacity_factor, as greedy / sampling do
+        try:
+            pcache, logits = self._prefill(input_ids, attention_mask, images, max_new_tokens)
+            B, nb, dev = logits.shape[0], num_beams, logits.device
+            cfg = self.config
+            cache = KVCache(cfg.num_hidden_layers, B * nb, pcache.smax, cfg.num_key_value_heads * cfg.head_dim, dev)
+            cache.lens.copy_(pcache.lens.repeat_interleave(nb))
+            K.kv_gather_rows(cache.tensors(), pcache.tensors(),
+                             torch.arange(B * nb, device=dev, dtype=torch.int32) // nb, cache.lens)
+            del pcache
+            logits = logits.repeat_interleave(nb, 0)
+            scorer = BeamSearchScorer(B, nb, max_new_tokens, length_penalty, early_stopping, eos_token_id, pad_token_id)
+            beam_scores = scorer.initial_beam_scores().to(dev)
+            while True:
+                cand = K.beam_topk(logits, beam_scores, nb).cpu()
+                tok, src, bs = scorer.step(*unpack_candidates(cand))
+                if scorer.is_done:
+                    break
+                nxt = torch.stack([tok.to(torch.int32), src.to(torch.int32), bs.view(torch.int32)]).to(dev)   # one copy
+                cache.reorder(nxt[1])
+                beam_scores = nxt[2].view(torch.float32)
+                logits = self._decode_step(nxt[0], cache)
+            seq, scores = scorer.finalize(num_return_sequences)
+        finally:
+            self.train(was_training)
+        seq, scores = seq.to(dev), scores.to(dev)
+        return BeamSearchOutput(seq, scores) if return_dict_in_generate else seq
 
     # ---- checkpoints in the reference's layout -----------------------------------------------------------------------
     def save_config(self, save_directory):

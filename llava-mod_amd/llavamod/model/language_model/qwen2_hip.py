@@ -66,9 +66,25 @@ class KVCache:
         self.v = [torch.zeros((B, smax, width), device=device, dtype=BF16) for _ in range(n_layers)]
         self.lens = torch.zeros(B, device=device, dtype=torch.int32)
         self.smax = smax
+        self._alt = None                  # beam search: second buffer set (k, v, pointer tables), allocated by the first reorder
 
     def get_seq_length(self):
         return int(self.lens.max())
+
+    def tensors(self):
+        return self.k + self.v
+
+    def reorder(self, src_row):
+        """Beam search: row r takes row src_row[r]'s cached positions [0, lens[r]) (device int32 [B]).  One kv_gather_rows launch
+        into the alternate buffers, which then become k / v (a gather by a permutation is not safe in place)."""
+        if self._alt is None:
+            n = len(self.k)
+            alt = [torch.empty_like(t) for t in self.tensors()]
+            self._alt = (alt[:n], alt[n:], K.ptr_table(alt), K.ptr_table(self.tensors()))
+        ak, av, alt_tab, cur_tab = self._alt
+        K.kv_gather_rows(ak + av, self.tensors(), src_row.to(torch.int32), self.lens, tables=(alt_tab, cur_tab))
+        self._alt = (self.k, self.v, cur_tab, alt_tab)
+        self.k, self.v = ak, av
 
 
 class Qwen2RMSNorm(nn.Module):
