@@ -442,10 +442,18 @@ __global__ __launch_bounds__(256) void moe_gate_bwd_kernel(const float* __restri
     const bool k2 = slot2[t] >= 0;
     const float g1 = k1 ? g[e1] : 0.f, g2 = k2 ? g[e2] : 0.f;
     const float sum = g1 + g2;
-    if (sum > 1.1920929e-07f) {
+    // w_j = g_j / clamp(g1 + g2, min = fp32 eps) (moe_finalize_kernel).  torch.clamp passes the gradient for sum >= eps;
+    // below it the denominator is the constant eps, so d w_j / d g_j = 1 / eps with no cross term.  That happens when the
+    // first pick was dropped and the surviving second pick's gate is tiny (a Gumbel-noise pick of an unlikely expert).
+    // sum == 0: both picks dropped, nothing to add.
+    if (sum >= 1.1920929e-07f) {
       const float u1 = dw1[t], u2 = dw2[t];
       const float common = (u1 * g1 + u2 * g2) / (sum * sum);
       const float d1 = u1 / sum - common, d2 = u2 / sum - common;
+#pragma unroll
+      for (int e = 0; e < ME; ++e) { if (k1 && e == e1) dg[e] += d1; if (k2 && e == e2) dg[e] += d2; }
+    } else if (sum > 0.f) {
+      const float d1 = dw1[t] / 1.1920929e-07f, d2 = dw2[t] / 1.1920929e-07f;
 #pragma unroll
       for (int e = 0; e < ME; ++e) { if (k1 && e == e1) dg[e] += d1; if (k2 && e == e2) dg[e] += d2; }
     }
@@ -755,7 +763,7 @@ int lmod_moe_dispatch_bwd(const void* d_in, const int* slot1, const int* slot2, 
   return lmod_launch_status();
 }
 
-// workspace: ceil(T/256) * E * H floats
+// workspace: ceil(T/64) * E * H floats (one partial per WG_SLAB-token slab)
 int lmod_moe_router_wgrad(const void* x, const float* dlogits, float* dwg, float* workspace, int T, int H, int E,
                           int accumulate, hipStream_t stream) {
   if (!x || !dlogits || !dwg || !workspace || T < 0 || H <= 0 || (H & 7) || E <= 0 || E > MAXE) return LMOD_EINVAL;
