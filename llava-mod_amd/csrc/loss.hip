@@ -15,7 +15,8 @@
 
 struct Online { float m, z; };
 __device__ __forceinline__ void on_add(Online& o, float v) {
-  if (v > o.m) { o.z = o.z * __expf(o.m - v) + 1.f; o.m = v; } else { o.z += __expf(v - o.m); }
+  // v == -inf adds nothing: with o.m == -inf too, exp(v - o.m) would be exp(NaN)
+  if (v > o.m) { o.z = o.z * __expf(o.m - v) + 1.f; o.m = v; } else if (v != -INFINITY) { o.z += __expf(v - o.m); }
 }
 __device__ __forceinline__ void on_merge(Online& a, const Online& b) {
   const float M = fmaxf(a.m, b.m);
@@ -118,8 +119,11 @@ __global__ __launch_bounds__(256) void rowloss_fwd_kernel(const bf16_t* __restri
   }
 }
 
-// ds[v] = ckd * (softmax_align(s)[v] - softmax_align(t)[v]) * [v < Va] + cce * (softmax_full(s)[v] - [v == label])
+// ds[v] = ckd * (fm * softmax_align(s)[v] - [s[v] finite] * softmax_align(t)[v]) * [v < Va]
+//       + cce * (softmax_full(s)[v] - [v == label])
 // ckd = kd_w[row] * kd_scale[seg], cce = ce_w[row] * ce_scale[seg]   (seg = seg_id ? seg_id[row] : 0)
+// The KD term is -ckd * d(x_kd)/ds with the reference's isinf(logp) mask: x = sum_v m_v p_v logp_v, m_v = [s[v] finite],
+// so dx/ds_v = m_v p_v - q_v fm with fm = sum_v m_v p_v (stats[:, 6]).  fm == 1.0f exactly on rows without -inf.
 __global__ __launch_bounds__(256) void rowloss_bwd_kernel(const bf16_t* s, long long ld_s, int Vs,
                                                          const bf16_t* __restrict__ t, long long ld_t, int Va,
                                                          const int* __restrict__ label, const float* __restrict__ stats,
@@ -134,7 +138,7 @@ __global__ __launch_bounds__(256) void rowloss_bwd_kernel(const bf16_t* s, long 
   const int sg = seg_id ? seg_id[row] : 0;
   const float ckd = (tr && kd_w && kd_scale) ? kd_w[row] * kd_scale[sg] : 0.f;
   const float cce = (ce_w && ce_scale) ? ce_w[row] * ce_scale[sg] : 0.f;
-  const float lse_f = st[0], lse_a = st[1], lse_t = st[2];
+  const float lse_f = st[0], lse_a = st[1], lse_t = st[2], fm = st[6];
   const int lb = label ? label[row] : -1;
   const int nca = Va >> 3, ncs = Vs >> 3;
   for (int c = tid; c < ncs; c += 256) {
@@ -154,7 +158,7 @@ __global__ __launch_bounds__(256) void rowloss_bwd_kernel(const bf16_t* s, long 
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float acc = 0.f;
-      if (al) acc += ckd * (__expf(g[k] - lse_a) - __expf(tf[k] - lse_t));
+      if (al) acc += ckd * (fm * __expf(g[k] - lse_a) - (g[k] > -INFINITY ? __expf(tf[k] - lse_t) : 0.f));
       if (cce != 0.f) acc += cce * (__expf(g[k] - lse_f) - ((c * 8 + k) == lb ? 1.f : 0.f));
       r[k] = acc;
     }

@@ -660,7 +660,7 @@ class DistillHead(torch.autograd.Function):
         Vs = head.w.shape[0]
         nseg = plan.seg_off.numel() - 1
         zero = torch.zeros(nseg, device=logits.device, dtype=torch.float32)
-        # rowloss_bwd computes ds = ckd*(q - p): that is -ckd * d(x_kd)/ds, hence the sign flip on g_kd
+        # rowloss_bwd computes ds = ckd*(fm q - m p): that is -ckd * d(x_kd)/ds, hence the sign flip on g_kd
         kd_scale = (-g_kd).contiguous().float() if g_kd is not None else zero
         ce_scale = g_ce.contiguous().float() if g_ce is not None else zero
         K.rowloss_bwd(logits, Vs, t_logits, ctx.Va, plan.ce_label, stats, plan.kd_w, plan.ce_w, plan.seg_id,
