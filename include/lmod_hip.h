@@ -261,6 +261,30 @@ int lmod_beam_topk_bf16(const void* logits, long long ld, int V, const float* be
 int lmod_kv_gather_rows(void* const* dst, const void* const* src, int ntensor, const int* src_row, const int* lens, int R,
                         int R_src, int smax_dst, int smax_src, int width, hipStream_t stream);
 
+/* ---- sampling (generate(do_sample=True); HF's temperature -> top-k -> top-p warpers, then one draw per row) ----------------
+ * lmod_sample_bf16: logits [R, ld] bf16 (V <= ld live columns), u [R] fp32 in [0, 1) (device; the library keeps no RNG state) ->
+ *   out_token [R].  x = logit / max(temperature, 1e-6) in fp32.  top-k applies when 0 < top_k < V and keeps x >= the k-th largest x
+ *   (all ties at that value).  top-p applies when top_p < 1: over the top-k survivors, renormalised and ordered by logit descending
+ *   (equal logits by the smaller token id), the shortest prefix whose mass reaches top_p (a token stays while the mass before it is
+ *   <= top_p); the nucleus is every token with x >= the logit of the prefix's last token, so the kept set is a threshold on the logit
+ *   and a tie group at the cutoff is kept whole.  That is at most part of one tie group more than a sort-based sampler keeps (it
+ *   cuts inside the group in the sort's unspecified order).  The maximum is always kept (top_p <= 0 keeps only its tie group).  The
+ *   draw is the inverse CDF over the kept set in token-id order: the first kept token whose cumulative kept mass exceeds
+ *   u * kept_mass (the last kept token if rounding would run past the end).
+ *   out_stats (nullable) [R][4] fp32: {logsumexp of x over all V, kept_mass / total_mass, number of kept tokens, cutoff logit
+ *   (unscaled bf16 value; -inf without a filter)}: the drawn token's log-probability under the warped distribution is
+ *   x[t] - stats[0] - log(stats[1]).
+ *   No sort: the cutoffs are thresholds on the 16-bit order-preserving key of the bf16 logit, found by radix selection with 256-bin
+ *   count + mass histograms (high byte, then low byte; one low-byte pass per active filter).  Masses are fixed-point integers
+ *   (exp(x - max) * 2^40 in 64 bits), so sums, the cutoff search and the inverse-CDF search are exact integer arithmetic and the
+ *   result is bit-for-bit reproducible; a token lighter than 2^-41 of the maximum weighs 0.  Rows are cut into chunks of `chunk`
+ *   tokens (a multiple of 8), grid = chunks x rows; 3 launches without a filter, 5 with one, 6 with both, no host read-back.
+ *   ws (8-byte aligned): ws_bytes >= R * (64 + 3072 * nh + 16 * ceil(V / chunk)), nh = 0 without a filter, 2 with one, 3 with both.
+ *   -inf logits are never drawn; a row without a finite logit gives token 0, lse -inf, kept fraction 0; NaN logits are unspecified
+ *   (the token stays in [0, V)).  R <= 65535, V >= 2; R == 0 is a no-op. */
+int lmod_sample_bf16(const void* logits, long long ld, int V, const float* u, int R, float temperature, int top_k, float top_p,
+                     int chunk, void* ws, long long ws_bytes, int* out_token, float* out_stats, hipStream_t stream);
+
 /* ---- sparse MoE (DeepSpeed 0.9.5 TopKGate/top1gating/top2gating/MOELayer semantics) ------------
  * logits[T,E] = x.float() @ wg^T  (TopKGate.forward; wg kept fp32).
  * Experts per layer: 1 <= E <= 32 (`--num_experts`, config/args.py:46); the per-token kernels are instantiated for

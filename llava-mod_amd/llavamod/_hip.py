@@ -53,6 +53,7 @@ SIGNATURES = {
     "lmod_attn_decode": "ppppp" + "iiiiiiii" + "f" + "p",
     "lmod_beam_topk_bf16": "pqi" + "p" + "iii" + "pq" + "ppp" + "p",
     "lmod_kv_gather_rows": "pp" + "i" + "pp" + "iiiii" + "p",
+    "lmod_sample_bf16": "pqi" + "pi" + "fif" + "i" + "pq" + "pp" + "p",
     "lmod_moe_router_fwd": "ppp" + "iii" + "p",
     "lmod_moe_gate": "pp" + "iiii" + "pppppppppppppp" + "iQQp" + "p",
     "lmod_moe_combine_fwd": "pppppp" + "ii" + "p",

@@ -1,4 +1,5 @@
-"""Beam-search bookkeeping of `generate(num_beams > 1)` in plain torch (no kernels, importable without the HIP library).
+"""Beam-search bookkeeping of `generate(num_beams > 1)` and the argument checks / result object of sampling, in plain torch (no
+kernels, importable without the HIP library).
 
 The semantics are HF `GenerationMixin._beam_search` (do_sample=False) of transformers 5.x, the version this project can run:
   * running beam scores start as [0, -1e9, ...] per sample; a step's candidates are the top 2*nb of
@@ -34,6 +35,25 @@ def check_beam_args(num_beams, num_return_sequences=1, do_sample=False, length_p
     if early_stopping not in (False, True):
         raise ValueError(f"early_stopping must be False or True, got {early_stopping!r}")
     float(length_penalty)
+
+
+def check_sample_args(do_sample=False, temperature=1.0, top_k=None, top_p=None, num_return_sequences=1):
+    """Arguments of `generate(num_beams=1)`: greedy returns one sequence per prompt (HF raises for more); sampling needs
+    temperature > 0, top_k None or a positive int, top_p None or in (0, 1]."""
+    n = num_return_sequences
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"num_return_sequences must be an int >= 1, got {n!r}")
+    if not do_sample:
+        if n != 1:
+            raise ValueError(f"greedy decoding returns one sequence per prompt: num_return_sequences={n} needs do_sample=True "
+                             "or num_beams > 1")
+        return
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not temperature > 0:
+        raise ValueError(f"temperature must be a number > 0 when do_sample=True, got {temperature!r}")
+    if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1):
+        raise ValueError(f"top_k must be None or a positive int, got {top_k!r}")
+    if top_p is not None and (isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0 < top_p <= 1):
+        raise ValueError(f"top_p must be None or in (0, 1], got {top_p!r}")
 
 
 class BeamSearchScorer:
@@ -145,3 +165,12 @@ class BeamSearchOutput:
 
     def __init__(self, sequences, sequences_scores):
         self.sequences, self.sequences_scores = sequences, sequences_scores
+
+
+class SampleOutput:
+    """`generate(do_sample=True, return_dict_in_generate=True)`: sequences int64 [B*n, L] (new tokens only, sample b's n
+    continuations in rows b*n .. b*n+n-1) and token_logprobs fp32 [B*n, L]: the log-probability of each drawn token under the
+    warped (temperature / top-k / top-p) distribution it was drawn from, 0 at positions after a sequence's EOS."""
+
+    def __init__(self, sequences, token_logprobs):
+        self.sequences, self.token_logprobs = sequences, token_logprobs

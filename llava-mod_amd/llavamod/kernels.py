@@ -440,6 +440,31 @@ def kv_gather_rows(dst, src, src_row, lens, tables=None):
          d0.shape[1], s0.shape[1], d0.shape[2])
 
 
+# ------------------------------------------------------------------------------------------ sampling
+def sample(logits, u, temperature=1.0, top_k=None, top_p=None, stats=False):
+    """logits [R, V] bf16 (row stride may exceed V), u [R] fp32 in [0, 1) on the device -> tokens int32 [R]: one draw per row from
+    the temperature / top-k / top-p warped distribution (HF's warper order; lmod_sample_bf16 in include/lmod_hip.h).  stats=True
+    also returns fp32 [R, 4]: {logsumexp of logits / T, kept mass fraction, number of kept tokens, cutoff logit}."""
+    R, V = logits.shape
+    assert logits.dtype == BF16 and logits.stride(1) == 1
+    assert u.dtype == torch.float32 and u.is_cuda and u.is_contiguous() and u.numel() == R
+    k = 0 if top_k is None else max(0, min(int(top_k), 2 ** 31 - 1))
+    p = 1.0 if top_p is None else float(top_p)
+    tokens = torch.empty(R, device=logits.device, dtype=torch.int32)
+    st = torch.empty((R, 4), device=logits.device, dtype=torch.float32) if stats else None
+    if R == 0:
+        return (tokens, st) if stats else tokens
+    # ~384 workgroups over all rows (one row alone would fill 1 of 256 CUs), chunks of at least 512 tokens: as beam_topk
+    c_target = max(1, min(-(-384 // R), -(-V // 512)))
+    chunk = (-(-V // c_target) + 7) // 8 * 8
+    C = -(-V // chunk)
+    nf = int(0 < k < V) + int(p < 1.0)
+    ws = torch.empty(R * (64 + 3072 * (nf + 1 if nf else 0) + 16 * C), device=logits.device, dtype=torch.uint8)
+    call("lmod_sample_bf16", ptr(logits), logits.stride(0), V, ptr(u), R, float(temperature), k, p, chunk, ptr(ws), ws.numel(),
+         ptr(tokens), ptr(st))
+    return (tokens, st) if stats else tokens
+
+
 # ------------------------------------------------------------------------------------------ MoE
 def moe_router_fwd(x, wg):
     T, H = x.shape

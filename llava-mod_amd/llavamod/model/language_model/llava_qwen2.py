@@ -225,6 +225,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         return cache, ops.linear_fwd(hidden, self.head())
 
     generation_budget = 512            # cache positions reserved beyond the prompt by a `use_cache=True` forward
+    sample_on_device = True            # generate(do_sample=True) draws with lmod_sample_bf16; False: the torch `_sample` (A/B baseline)
 
     @torch.no_grad()
     def _cached_forward(self, input_ids, attention_mask, images, past, out_cls):
@@ -269,28 +270,55 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         """Generation with a KV cache (the reference's eval path calls HF `generate` on the Eval model,
         llava_qwen2_moe.py:629-681; its serving code passes do_sample / temperature / top_p, its eval scripts num_beams).
         Greedy by default; do_sample=True draws from the temperature / top-k / top-p filtered distribution (`seed` makes the
-        draw reproducible); num_beams > 1 is beam search (`_beam_generate`).  Right-padded prompts: every sample continues
-        from its own length.  Returns the NEW tokens [B, <= max_new_tokens] (int64; positions after a sample's EOS hold
-        pad_token_id)."""
+        draw reproducible) and returns num_return_sequences independent continuations per prompt; num_beams > 1 is beam search
+        (`_beam_generate`).  Every mode selects its tokens on the device (lmod_row_argmax_bf16 / lmod_sample_bf16 /
+        lmod_beam_topk_bf16).  Right-padded prompts: every sample continues from its own length.  Returns the NEW tokens
+        [B * num_return_sequences, <= max_new_tokens] (int64; sample b's continuations in rows b*n .. b*n+n-1; positions after a
+        sequence's EOS hold pad_token_id); with do_sample and return_dict_in_generate a `SampleOutput` (sequences, token_logprobs)."""
         if num_beams != 1:
             return self._beam_generate(input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, do_sample,
                                        num_beams, num_return_sequences, length_penalty, early_stopping, return_dict_in_generate)
+        from ...generation import SampleOutput, check_sample_args
+        check_sample_args(do_sample, temperature, top_k, top_p, num_return_sequences)
+        n = num_return_sequences
+        on_device = do_sample and self.sample_on_device
         was_training = self.training
         self.eval()
         cache, logits = self._prefill(input_ids, attention_mask, images, max_new_tokens)
-        B = logits.shape[0]
+        B, dev = logits.shape[0], logits.device
+        if n > 1:
+            # one prefill at B rows, its cache replicated into B*n rows (as the beams of _beam_generate)
+            cfg = self.config
+            pcache, cache = cache, KVCache(cfg.num_hidden_layers, B * n, cache.smax, cfg.num_key_value_heads * cfg.head_dim, dev)
+            cache.lens.copy_(pcache.lens.repeat_interleave(n))
+            K.kv_gather_rows(cache.tensors(), pcache.tensors(), torch.arange(B * n, device=dev, dtype=torch.int32) // n, cache.lens)
+            del pcache
+            logits = logits.repeat_interleave(n, 0)
+            B = B * n
         pad = eos_token_id if pad_token_id is None else pad_token_id
-        done = torch.zeros(B, dtype=torch.bool, device=logits.device)
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
         gen = None
         if do_sample:
-            gen = torch.Generator(device=logits.device)
+            gen = torch.Generator(device=dev)
             # no `seed`: DRAW one from the global generator (deterministic under torch.manual_seed) — never reseed it: torch.seed()
             # would change torch.initial_seed(), from which the MoE layers derive their gating-noise stream, so a sampling
             # generate() between two training steps would silently fork the training run (ADVICE r03)
             gen.manual_seed(int(seed) if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
-        out = []
+        want_lp = on_device and return_dict_in_generate
+        out, lps = [], []
         for step in range(max_new_tokens):
-            nxt = self._sample(logits, temperature, top_k, top_p, gen) if do_sample else K.row_argmax(logits)
+            if on_device:
+                # one uniform per row; the draw, its filter and its statistics are lmod_sample_bf16
+                u = torch.rand(B, generator=gen, device=dev)
+                nxt = K.sample(logits, u, temperature, top_k, top_p, stats=want_lp)
+                if want_lp:
+                    nxt, st = nxt
+                    # log p(token) under the warped distribution: x[t] - lse - log(kept fraction); a gather of B logits
+                    x = logits.gather(1, nxt.long()[:, None]).squeeze(1).double() / max(float(temperature), 1e-6)
+                    lp = (x - st[:, 0].double() - torch.log(st[:, 1].double())).clamp(max=0.0).float()
+                    lps.append(torch.where(done, torch.zeros_like(lp), lp))
+            else:
+                nxt = self._sample(logits, temperature, top_k, top_p, gen) if do_sample else K.row_argmax(logits)
             tok = nxt.long()
             if eos_token_id is not None:
                 tok = torch.where(done, torch.full_like(tok, pad if pad is not None else 0), tok)
@@ -300,7 +328,10 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                 break
             logits = self._decode_step(nxt, cache)
         self.train(was_training)
-        return torch.stack(out, 1)
+        seq = torch.stack(out, 1)
+        if do_sample and return_dict_in_generate:
+            return SampleOutput(seq, torch.stack(lps, 1) if lps else None)
+        return seq
 
     @torch.no_grad()
     def _beam_generate(self, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, do_sample, num_beams,
