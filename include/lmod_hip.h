@@ -221,6 +221,38 @@ int lmod_attn_bwd_split(const void* Q, const void* K, const void* V, const void*
 int lmod_attn_decode(const void* q, const void* kcache, const void* vcache, const int* lens, void* out, int B, int nh,
                      int nkv, int hd, int smax, int ldq, int ld_cache, int ldo, float scale, hipStream_t stream);
 
+/* ---- multi-token cache extension and greedy assisted decoding (csrc/append.hip) ----------------------------------------
+ * lmod_attn_append: attention of a chunk of new queries against a KV cache that already holds the chunk's own keys and values.
+ *   Caches [B, smax, ld_cache] (kv head hk at column hk*hd), lens[b] = valid positions AFTER the append.  Sample b brings n_b new
+ *   tokens, 0 <= n_b <= T (0: the sample has no row and nothing is computed or written for it): packed query rows q[cu_new[b] + t], t < n_b (cu_new: device int[B+1]; NULL: every sample brings exactly
+ *   T tokens, row b*T + t — the cu_seqlens convention of lmod_attn_fwd); output rows are laid out like q.  Query t of sample b sees
+ *   the keys k <= lens[b] - n_b + t; a row without a visible key is exactly 0.  hd 64 or 128, nh % nkv == 0,
+ *   1 <= T <= T_MAX = 16 and (nh / nkv) * T <= 128 (LMOD_EUNSUPPORTED beyond).  fp32 throughout, one rounding to bf16 at the output.
+ *   The key range is split over `nsplit` workgroups per (sample, kv head) whose (m, l, O) partials a second launch merges in split
+ *   order (deterministic): nsplit = 0 lets the library choose (lmod_attn_append_nsplit(B, nkv, smax), less if ws is smaller, 1
+ *   without ws), 1 <= nsplit <= 32 forces a count.  ws: 16-byte aligned, ws_bytes >= nsplit * B * nh * T * (hd + 2) * 4 when
+ *   nsplit > 1.  T = 1 computes what lmod_attn_decode computes (other summation order).
+ * lmod_kv_append_rows: the chunk's post-RoPE K and V columns out of the fused QKV buffer (row cu_new[b] + t, K at column kcol, V at
+ *   vcol, `width` = nkv*hd columns each, all multiples of 8) into kcache / vcache [B, smax, ld_cache] at position
+ *   lens_before[b] + t, one launch for both tensors.  max_len_after: the caller's upper bound of lens_before[b] + n_b;
+ *   LMOD_EINVAL if it exceeds smax (grow the cache first) — the device never clamps a position.
+ * lmod_spec_accept: the acceptance rule of greedy assisted decoding.  draft [B, k], target [B, k+1] (argmax of the k+1 verification
+ *   rows), 1 <= k < T_MAX; done [B] (in/out), eos (< 0: none), pad.  n_acc[b] = length of the longest prefix with
+ *   draft[b, i] == target[b, i] (0 for a sample already done).  Emitted: draft[b, 0:n_acc] then target[b, n_acc], cut after the
+ *   first eos (which sets done[b]); a sample already done emits nothing.  out [B, k+5] int32: columns 0..k the emitted tokens
+ *   (pad behind them), k+1 n_acc, k+2 the number of emitted tokens, k+3 next_token, k+4 done; next_token [B] = target[b, n_acc]
+ *   (pad once done).  lens_target (in: after the k+1-token verification append) -= k - n_acc; lens_draft (in: after the k draft
+ *   steps) -= k - min(n_acc + 1, k): both caches then hold the prompt and every emitted token except next_token (the draft also
+ *   lacks its k-th draft when all k were accepted); positions behind lens are dead and are overwritten by the next round. */
+int lmod_attn_append_nsplit(int B, int nkv, int smax);
+int lmod_attn_append(const void* q, const void* kcache, const void* vcache, const int* lens, const int* cu_new, void* out, int B,
+                     int T, int nh, int nkv, int hd, int smax, int ldq, int ld_cache, int ldo, float scale, int nsplit, void* ws,
+                     long long ws_bytes, hipStream_t stream);
+int lmod_kv_append_rows(const void* qkv, int ldqkv, int kcol, int vcol, int width, const int* cu_new, const int* lens_before,
+                        void* kcache, void* vcache, int B, int T, int smax, int ld_cache, int max_len_after, hipStream_t stream);
+int lmod_spec_accept(const int* draft, const int* target, int k, int* done, int eos, int pad, int* lens_target, int* lens_draft,
+                     int* out, int* next_token, int B, hipStream_t stream);
+
 /* ---- multimodal splice / loss-row plans built on the device ----------------------------------------
  * prepare_inputs_labels_for_multimodal (llava_arch.py:155-334) as index maps, from int tensors already on the device.
  * lmod_splice_count: per sample the spliced length (pads stripped by attention_mask, every -200 token replaced by

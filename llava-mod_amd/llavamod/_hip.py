@@ -51,6 +51,10 @@ SIGNATURES = {
     "lmod_lossplan_fill": "p" + "iiiii" + "p" + "ppppppp" + "p",
     "lmod_row_argmax_bf16": "pqi" + "pi" + "p",
     "lmod_attn_decode": "ppppp" + "iiiiiiii" + "f" + "p",
+    "lmod_attn_append_nsplit": "iii",                      # host-side query, no stream: call it through load()
+    "lmod_attn_append": "pppppp" + "iiiiiiiii" + "f" + "i" + "pq" + "p",
+    "lmod_kv_append_rows": "piiii" + "pp" + "pp" + "iiiii" + "p",
+    "lmod_spec_accept": "pp" + "i" + "p" + "ii" + "pppp" + "i" + "p",
     "lmod_beam_topk_bf16": "pqi" + "p" + "iii" + "pq" + "ppp" + "p",
     "lmod_kv_gather_rows": "pp" + "i" + "pp" + "iiiii" + "p",
     "lmod_sample_bf16": "pqi" + "pi" + "fif" + "i" + "pq" + "pp" + "p",

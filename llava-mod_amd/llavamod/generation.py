@@ -161,10 +161,11 @@ def unpack_candidates(block):
 
 class BeamSearchOutput:
     """`generate(num_beams > 1, return_dict_in_generate=True)`: sequences int64 [B*n, L] (new tokens only, best first per sample)
-    and sequences_scores fp32 [B*n] (length-normalised sum of log-probabilities)."""
+    and sequences_scores fp32 [B*n] (length-normalised sum of log-probabilities).  past_key_values: the cache of the B*num_beams
+    RUNNING beams in their last step's order — NOT aligned with the rows of `sequences` (finalized hypotheses)."""
 
-    def __init__(self, sequences, sequences_scores):
-        self.sequences, self.sequences_scores = sequences, sequences_scores
+    def __init__(self, sequences, sequences_scores, past_key_values=None):
+        self.sequences, self.sequences_scores, self.past_key_values = sequences, sequences_scores, past_key_values
 
 
 class SampleOutput:
@@ -172,5 +173,108 @@ class SampleOutput:
     continuations in rows b*n .. b*n+n-1) and token_logprobs fp32 [B*n, L]: the log-probability of each drawn token under the
     warped (temperature / top-k / top-p) distribution it was drawn from, 0 at positions after a sequence's EOS."""
 
-    def __init__(self, sequences, token_logprobs):
-        self.sequences, self.token_logprobs = sequences, token_logprobs
+    def __init__(self, sequences, token_logprobs, past_key_values=None):
+        self.sequences, self.token_logprobs, self.past_key_values = sequences, token_logprobs, past_key_values
+
+
+class GreedyOutput:
+    """`generate(return_dict_in_generate=True)` without sampling or beams: sequences int64 [B, L] (new tokens only) and the KV cache."""
+
+    def __init__(self, sequences, past_key_values=None):
+        self.sequences, self.past_key_values = sequences, past_key_values
+
+
+# ---------------------------------------------------------------------------------------------- assisted (speculative) decoding
+class AssistedOutput:
+    """`generate(assistant_model=..., return_dict_in_generate=True)`: sequences int64 [B, L] (new tokens only), num_rounds (draft /
+    verify rounds), num_target_forwards (the prefill plus one verification pass per round), num_accepted int64 [B] (draft tokens that
+    were emitted) and the target's KV cache (when max_new_tokens cut the last round short it holds accepted tokens behind the
+    returned ones)."""
+
+    def __init__(self, sequences, num_rounds, num_target_forwards, num_accepted, past_key_values=None):
+        self.sequences, self.num_rounds, self.num_target_forwards = sequences, num_rounds, num_target_forwards
+        self.num_accepted, self.past_key_values = num_accepted, past_key_values
+
+
+def check_assisted_args(do_sample, num_beams, num_assistant_tokens, t_max, num_return_sequences=1):
+    if do_sample or num_beams != 1:
+        raise ValueError("assistant_model supports greedy decoding only: do_sample=True and num_beams > 1 cannot be combined with it")
+    if num_return_sequences != 1:
+        raise ValueError("greedy assisted decoding returns one sequence per prompt")
+    k = num_assistant_tokens
+    if not isinstance(k, int) or not 1 <= k <= t_max - 1:
+        raise ValueError(f"num_assistant_tokens must be an int in 1..{t_max - 1}, got {k!r}")
+
+
+def spec_accept(draft, target, done, eos, pad, lens_target, lens_draft):
+    """The acceptance rule of greedy assisted decoding in plain torch — what lmod_spec_accept computes on the device (the product path
+    calls the kernel; this is the statement the tests hold both against).  draft [B, k], target [B, k+1], done [B] (bool / int), lens
+    [B]; eos None: no stop token.  Returns (block [B, k+5] = emitted tokens (pad behind) | n_acc | n_emitted | next_token | done,
+    next_token [B], done [B], lens_target [B], lens_draft [B]) without modifying its inputs."""
+    B, k = draft.shape
+    done = done.bool()
+    padv = 0 if pad is None else int(pad)
+    match = (draft == target[:, :k]).long()
+    n_acc = match.cumprod(1).sum(1)
+    n_acc = torch.where(done, torch.zeros_like(n_acc), n_acc)
+    idx = torch.arange(k + 1, device=draft.device)[None, :]
+    corrected = target.gather(1, n_acc[:, None])
+    tokens = torch.where(idx < n_acc[:, None], torch.cat([draft, draft[:, -1:]], 1), corrected.expand(B, k + 1))
+    n_emit = torch.where(done, torch.zeros_like(n_acc), n_acc + 1)
+    fin = done.clone()
+    if eos is not None:
+        is_eos = (tokens == int(eos)) & (idx < n_emit[:, None])
+        first = torch.where(is_eos.any(1), is_eos.long().argmax(1), torch.full_like(n_acc, k + 1))
+        n_emit = torch.minimum(n_emit, first + 1)
+        fin = fin | is_eos.any(1)
+    tokens = torch.where(idx < n_emit[:, None], tokens, torch.full_like(tokens, padv))
+    nxt = torch.where(fin, torch.full_like(n_acc, padv), corrected[:, 0].long())
+    block = torch.cat([tokens.long(), n_acc[:, None], n_emit[:, None], nxt[:, None], fin.long()[:, None]], 1)
+    return (block, nxt, fin, lens_target.long() - k + n_acc, lens_draft.long() - k + torch.clamp(n_acc + 1, max=k))
+
+
+class AssistedBookkeeper:
+    """Host-side bookkeeping of the assisted loop: the output buffer, how many tokens every sample holds, which samples have stopped
+    (EOS or max_new_tokens, possibly in the middle of a round) and the statistics.  Fed with the first token (the target's prefill
+    argmax) and then one int block [B, k+5] per round (spec_accept's layout), all on the host."""
+
+    def __init__(self, B, k, max_new_tokens, eos, pad):
+        self.B, self.k, self.max_new, self.eos = B, k, max_new_tokens, eos
+        self.pad = 0 if pad is None else int(pad)
+        self.seq = torch.full((B, max_new_tokens), self.pad, dtype=torch.int64)
+        self.n = torch.zeros(B, dtype=torch.int64)
+        self.stopped = torch.zeros(B, dtype=torch.bool)
+        self.num_accepted = torch.zeros(B, dtype=torch.int64)
+        self.num_rounds = 0
+
+    def first(self, tokens):
+        """tokens [B]: the target's first token.  Returns done [B] (bool) for the device-side flag."""
+        tokens = tokens.long().cpu()
+        self.seq[:, 0] = tokens
+        self.n += 1
+        done = (tokens == self.eos) if self.eos is not None else torch.zeros(self.B, dtype=torch.bool)
+        self.stopped = done | (self.n >= self.max_new)
+        return done
+
+    def update(self, block):
+        """One round's block [B, k+5]: append every sample's emitted tokens, cut at max_new_tokens."""
+        k = self.k
+        block = block.long().cpu()
+        live = ~self.stopped
+        n_emit = torch.where(live, block[:, k + 2], torch.zeros_like(self.n))
+        take = torch.minimum(n_emit, self.max_new - self.n)
+        idx = torch.arange(k + 1)[None, :]
+        mask = idx < take[:, None]
+        rows = torch.arange(self.B)[:, None].expand(self.B, k + 1)
+        self.seq[rows[mask], (self.n[:, None] + idx)[mask]] = block[:, :k + 1][mask]
+        self.num_accepted += torch.minimum(block[:, k + 1], take)
+        self.n = self.n + take
+        self.stopped = self.stopped | (block[:, k + 4] != 0) | (self.n >= self.max_new)
+        self.num_rounds += 1
+
+    @property
+    def finished(self):
+        return bool(self.stopped.all())
+
+    def sequences(self):
+        return self.seq[:, :int(self.n.max())]

@@ -399,6 +399,65 @@ def attn_decode(q, kcache, vcache, lens, nh, nkv, hd, scale):
     return out
 
 
+# ------------------------------------------------------------------------------------------ multi-token cache extension
+APPEND_T_MAX = 16          # csrc/append.hip: tokens per sample in one chunk; (nh / nkv) * T <= 128 as well
+_APPEND_WS = {}
+
+
+def attn_append_nsplit(B, nkv, smax):
+    """The key-split count lmod_attn_append chooses by itself for these shapes (host-side query)."""
+    return int(_hip.load().lmod_attn_append_nsplit(int(B), int(nkv), int(smax)))
+
+
+def attn_append(q, kcache, vcache, lens, nh, nkv, hd, scale, T, cu_new=None, nsplit=0):
+    """A chunk of new queries against caches that already hold the chunk's keys / values.  q [R, nh*hd] packed rows (views fine):
+    sample b owns rows cu_new[b] .. cu_new[b+1]-1 (device int32 [B+1]; None: exactly T rows per sample), 0..T rows, T <= APPEND_T_MAX;
+    lens [B] int32 = valid positions after the append.  Query t of sample b sees keys k <= lens[b] - n_b + t.  -> out [R, nh*hd].
+    nsplit: 0 lets the library split the key range over workgroups, 1..32 forces a count (tests, timing)."""
+    B = kcache.shape[0]
+    assert q.dtype == BF16 and q.stride(1) == 1 and kcache.dtype == BF16 and vcache.dtype == BF16
+    assert kcache.stride(2) == 1 and vcache.stride() == kcache.stride() and kcache.stride(0) == kcache.shape[1] * kcache.stride(1)
+    assert lens.dtype == torch.int32 and lens.numel() == B and (cu_new is None or (cu_new.dtype == torch.int32 and cu_new.numel() == B + 1))
+    assert cu_new is not None or q.shape[0] == B * T
+    out = torch.empty((q.shape[0], nh * hd), device=q.device, dtype=BF16)
+    ns = nsplit if nsplit else attn_append_nsplit(B, nkv, kcache.shape[1])
+    ws, need = None, ns * B * nh * T * (hd + 2) * 4 if ns > 1 else 0
+    if need:
+        key = (q.device, _hip.stream())     # one workspace per device AND stream, grown on demand (launches on one stream are ordered)
+        ws = _APPEND_WS.get(key)
+        if ws is None or ws.numel() < need:
+            _APPEND_WS[key] = ws = torch.empty(need, device=q.device, dtype=torch.uint8)
+    call("lmod_attn_append", ptr(q), ptr(kcache), ptr(vcache), ptr(lens), ptr(cu_new), ptr(out), B, T, nh, nkv, hd, kcache.shape[1],
+         q.stride(0), kcache.stride(1), out.stride(0), float(scale), ns, ptr(ws), need)
+    return out
+
+
+def kv_append_rows(qkv, kcol, vcol, width, kcache, vcache, lens_before, T, max_len_after, cu_new=None):
+    """kcache[b, lens_before[b] + t] = qkv[row(b, t), kcol:kcol+width] and the same for vcache / vcol, one launch; row(b, t) =
+    cu_new[b] + t (None: b*T + t).  max_len_after: host upper bound of lens_before[b] + n_b — beyond the cache's smax this raises
+    (LMOD_EINVAL) instead of clamping."""
+    B, smax = kcache.shape[0], kcache.shape[1]
+    assert qkv.dtype == BF16 and qkv.stride(1) == 1 and kcache.dtype == BF16 and vcache.stride() == kcache.stride()
+    assert kcache.stride(2) == 1 and kcache.stride(0) == smax * kcache.stride(1) and lens_before.dtype == torch.int32
+    call("lmod_kv_append_rows", ptr(qkv), qkv.stride(0), kcol, vcol, width, ptr(cu_new), ptr(lens_before), ptr(kcache), ptr(vcache),
+         B, T, smax, kcache.stride(1), int(max_len_after))
+
+
+def spec_accept(draft, target, done, eos, pad, lens_target, lens_draft):
+    """Greedy assisted decoding's acceptance rule on the device (lmod_spec_accept in include/lmod_hip.h).  draft [B, k], target
+    [B, k+1], done [B], the two caches' lens [B]: int32, contiguous; done and the lens are updated in place.  Returns (block
+    [B, k+5] int32: emitted tokens | n_acc | n_emitted | next_token | done, next_token [B] int32)."""
+    B, k = draft.shape
+    for t in (draft, target, done, lens_target, lens_draft):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert tuple(target.shape) == (B, k + 1) and done.numel() == B
+    out = torch.empty((B, k + 5), device=draft.device, dtype=torch.int32)
+    nxt = torch.empty(B, device=draft.device, dtype=torch.int32)
+    call("lmod_spec_accept", ptr(draft), ptr(target), k, ptr(done), -1 if eos is None else int(eos), 0 if pad is None else int(pad),
+         ptr(lens_target), ptr(lens_draft), ptr(out), ptr(nxt), B)
+    return out, nxt
+
+
 # ------------------------------------------------------------------------------------------ beam search
 def beam_topk(logits, beam_scores, nb):
     """logits [B*nb, V] bf16 (row stride may exceed V), beam_scores [B*nb] fp32 -> one int32 block [3, B, 2*nb]: per sample the top

@@ -235,11 +235,81 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
             cache, logits = self._prefill(input_ids, attention_mask, images, self.generation_budget)
         else:
             cache = past
+            dev = cache.lens.device
+            if input_ids.shape[1] > 1:           # a chunk of new tokens: fp32 logits [B, T, V], rows of padded positions zero; grows the cache
+                return out_cls(loss=None, logits=self._append_chunk(input_ids, attention_mask, cache, "all"), past_key_values=cache)
             if int(cache.lens.max()) >= cache.smax:
                 raise ValueError("KV cache exhausted: raise `generation_budget` before the prefill")
-            dev = cache.lens.device
             logits = self._decode_step(input_ids[:, -1].to(device=dev, dtype=torch.int32), cache)
         return out_cls(loss=None, logits=logits.float().unsqueeze(1), past_key_values=cache)
+
+    @torch.no_grad()
+    def _append_chunk(self, input_ids, attention_mask, cache, want, reserve=0):
+        """Push input_ids [B, T] (text only; attention_mask None or [B, T], right-padded, covering the chunk only) through the model
+        against `cache` — the continuation of a conversation — in pieces of at most APPEND_T_MAX tokens per sample
+        (Qwen2Model.forward_append; only live rows enter the decoder).  The cache grows if it has to (plus `reserve` positions).
+        want="all": fp32 logits [B, T, V] with zero rows on padded positions; want="last": bf16 logits [B, V] of every sample's last
+        live token."""
+        from ...constants import IMAGE_TOKEN_INDEX
+        dev = cache.lens.device
+        ids = input_ids.to(dev)
+        B, T = ids.shape
+        if B != cache.lens.shape[0]:
+            raise ValueError(f"the cache holds {cache.lens.shape[0]} samples, input_ids {B}")
+        if bool((ids == IMAGE_TOKEN_INDEX).any()):
+            raise ValueError("image tokens in a continuation chunk are not supported: a chunk fed with past_key_values is text-only")
+        if attention_mask is not None:
+            amd = attention_mask.to(device=dev).to(torch.int32)
+            if tuple(amd.shape) != (B, T):
+                raise ValueError("with past_key_values and more than one new token the attention_mask covers the chunk only: [B, T]")
+            if bool((amd[:, 1:] > amd[:, :-1]).any()):
+                raise ValueError("generate/use_cache expects RIGHT-padded prompts (attention_mask must be non-increasing along "
+                                 "the sequence); left padding is not supported on this path")
+            n_all = amd.sum(1).to(torch.int32)
+            if bool((n_all < 1).any()):
+                raise ValueError("every sample of a continuation chunk needs at least one live token")
+        else:
+            n_all = torch.full((B,), T, device=dev, dtype=torch.int32)
+        n_host = n_all.cpu()
+        hi = int(cache.lens.max())
+        if hi + T + reserve > cache.smax:
+            cache.grow(hi + T + reserve)
+        emb_w = self.model.embed_tokens.weight
+        V = self.lm_head.weight.shape[0]
+        out = torch.zeros((B, T, V), device=dev, dtype=torch.float32) if want == "all" else torch.empty((B, V), device=dev, dtype=BF16)
+        for j0 in range(0, T, K.APPEND_T_MAX):
+            Tp = min(K.APPEND_T_MAX, T - j0)
+            n_p = (n_all - j0).clamp(0, Tp).to(torch.int32)
+            nh_p = (n_host - j0).clamp(0, Tp)
+            R = int(nh_p.sum())
+            if R == 0:
+                break
+            live = torch.arange(Tp, device=dev)[None, :] < n_p[:, None]
+            uniform = R == B * Tp
+            tok = ids[:, j0:j0 + Tp][live].to(torch.int32).contiguous()                 # packed, sample-major
+            emb = K.gather_rows(emb_w, None, tok, emb_w.shape[1])
+            hidden = self.model.forward_append(emb, cache, Tp if uniform else n_p, T=Tp, max_len=hi + j0)
+            lg = ops.linear_fwd(hidden, self.head())
+            if want == "all":
+                out[:, j0:j0 + Tp][live] = lg.float()
+            else:
+                ends = (nh_p > 0) & (n_host <= j0 + Tp)                                  # samples whose last live token is in this piece
+                rows = (nh_p.cumsum(0) - 1)[ends].to(dev)
+                out[ends.to(dev)] = lg[rows]
+        return out
+
+    def _start(self, input_ids, attention_mask, images, max_new_tokens, past):
+        """Where every generation mode begins: the prompt's prefill, or — continuing from `past` — the new turn's tokens through the chunk
+        path.  Returns (cache with room for max_new_tokens more positions, bf16 logits [B, V] of every sample's last token)."""
+        if past is None:
+            return self._prefill(input_ids, attention_mask, images, max_new_tokens)
+        if images is not None:
+            raise ValueError("a continuation (past_key_values) is text-only: images belong to the first turn")
+        if input_ids.shape[1] == 1:
+            if int(past.lens.max()) + 1 + max_new_tokens > past.smax:
+                past.grow(int(past.lens.max()) + 1 + max_new_tokens)
+            return past, self._decode_step(input_ids[:, 0].to(device=past.lens.device, dtype=torch.int32), past)
+        return past, self._append_chunk(input_ids, attention_mask, past, "last", reserve=max_new_tokens)
 
     @torch.no_grad()
     def _decode_step(self, tokens, cache):
@@ -266,7 +336,8 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, images=None, max_new_tokens=16, eos_token_id=None,
                  pad_token_id=None, do_sample=False, temperature=1.0, top_k=None, top_p=None, seed=None, num_beams=1,
-                 num_return_sequences=1, length_penalty=1.0, early_stopping=False, return_dict_in_generate=False, **kwargs):
+                 num_return_sequences=1, length_penalty=1.0, early_stopping=False, return_dict_in_generate=False,
+                 past_key_values=None, assistant_model=None, num_assistant_tokens=5, **kwargs):
         """Generation with a KV cache (the reference's eval path calls HF `generate` on the Eval model,
         llava_qwen2_moe.py:629-681; its serving code passes do_sample / temperature / top_p, its eval scripts num_beams).
         Greedy by default; do_sample=True draws from the temperature / top-k / top-p filtered distribution (`seed` makes the
@@ -274,17 +345,36 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         (`_beam_generate`).  Every mode selects its tokens on the device (lmod_row_argmax_bf16 / lmod_sample_bf16 /
         lmod_beam_topk_bf16).  Right-padded prompts: every sample continues from its own length.  Returns the NEW tokens
         [B * num_return_sequences, <= max_new_tokens] (int64; sample b's continuations in rows b*n .. b*n+n-1; positions after a
-        sequence's EOS hold pad_token_id); with do_sample and return_dict_in_generate a `SampleOutput` (sequences, token_logprobs)."""
+        sequence's EOS hold pad_token_id); with do_sample and return_dict_in_generate a `SampleOutput` (sequences, token_logprobs).
+
+        past_key_values (a KVCache of an earlier generate() / use_cache forward): continue from it — `input_ids` [B, T] (and an
+        optional right-padded attention_mask [B, T]) are the NEW turn only, text-only, and run through the chunk path
+        (`_append_chunk`) instead of a prefill; every mode works from there.  The cache holds each position that was fed: the prompt
+        and every generated token but each row's last, which a caller chaining turns puts in front of the next turn's tokens.
+        With return_dict_in_generate every mode's result carries `past_key_values`.  NOTE, a change of an existing path: greedy
+        generate(return_dict_in_generate=True) used to return the bare token tensor and now returns a `GreedyOutput` (sequences,
+        past_key_values) — the only way to hand a greedy turn's cache on.  Beam search: the cache holds the B * num_beams RUNNING
+        beams in their last step's order; its rows are not the rows of `sequences` (finalized hypotheses, best first), so it
+        cannot be chained from without picking rows.  Assisted decoding: when max_new_tokens cuts a round short the target's cache
+        holds accepted tokens behind the returned ones.
+
+        assistant_model (with num_assistant_tokens = k in 1..APPEND_T_MAX-1): greedy assisted decoding, `_assisted_generate`."""
+        if assistant_model is not None:
+            from ...generation import check_assisted_args
+            check_assisted_args(do_sample, num_beams, num_assistant_tokens, K.APPEND_T_MAX, num_return_sequences)
+            return self._assisted_generate(input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id,
+                                           assistant_model, num_assistant_tokens, return_dict_in_generate, past_key_values)
         if num_beams != 1:
             return self._beam_generate(input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, do_sample,
-                                       num_beams, num_return_sequences, length_penalty, early_stopping, return_dict_in_generate)
-        from ...generation import SampleOutput, check_sample_args
+                                       num_beams, num_return_sequences, length_penalty, early_stopping, return_dict_in_generate,
+                                       past_key_values)
+        from ...generation import GreedyOutput, SampleOutput, check_sample_args
         check_sample_args(do_sample, temperature, top_k, top_p, num_return_sequences)
         n = num_return_sequences
         on_device = do_sample and self.sample_on_device
         was_training = self.training
         self.eval()
-        cache, logits = self._prefill(input_ids, attention_mask, images, max_new_tokens)
+        cache, logits = self._start(input_ids, attention_mask, images, max_new_tokens, past_key_values)
         B, dev = logits.shape[0], logits.device
         if n > 1:
             # one prefill at B rows, its cache replicated into B*n rows (as the beams of _beam_generate)
@@ -330,12 +420,95 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         self.train(was_training)
         seq = torch.stack(out, 1)
         if do_sample and return_dict_in_generate:
-            return SampleOutput(seq, torch.stack(lps, 1) if lps else None)
+            return SampleOutput(seq, torch.stack(lps, 1) if lps else None, cache)
+        return GreedyOutput(seq, cache) if return_dict_in_generate else seq
+
+    @torch.no_grad()
+    def _assisted_generate(self, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, draft, k,
+                           return_dict_in_generate, past=None):
+        """Greedy assisted (speculative) decoding, HF `generate(assistant_model=draft)`: this model is the target, `draft` (same
+        tokenizer; e.g. the distilled student) proposes k tokens per round.  Both models prefill the same prompt and images, each
+        with its own tower and projector.  Per round: (1) the draft runs its decode steps, argmax on the device; (2) the target runs
+        ONE forward_append over [next_token, d_1 .. d_k]; (3) lmod_row_argmax_bf16 over the k+1 logit rows; (4) lmod_spec_accept
+        (longest matching prefix, the corrected token, EOS, both caches' lens — a rejected draft costs no copy); (5) the draft
+        catches up through its own forward_append with 1 or 2 tokens per sample ([d_k,] next_token — ragged), whose last row also
+        gives the next round's first draft token, so later rounds run k-1 draft decode steps.  The host reads one int block
+        [B, k+5] back per round (stop test and output).  Both argmaxes run over min(V_draft, V_target) columns, so the draft can
+        never hand the target an id it has no embedding for.  The result equals plain greedy of the target wherever the chunk and
+        the decode path agree on the argmax (they differ in summation order: away from ties).  A MoE model as target routes the
+        B * (k+1) rows of a verification pass with the eval capacity rule over the rows of that call, as a decode step does over
+        its B rows.  Returns the new tokens [B, <= max_new_tokens]; with return_dict_in_generate an `AssistedOutput`."""
+        from ...generation import AssistedBookkeeper, AssistedOutput
+        if past is not None:
+            raise ValueError("assistant_model cannot continue from past_key_values: the draft model has no cache of the earlier turns")
+        modes = (self.training, draft.training)
+        self.eval(), draft.eval()
+        try:
+            tcache, tlogits = self._start(input_ids, attention_mask, images, max_new_tokens + k + 1, None)
+            dcache, _ = draft._start(input_ids, attention_mask, images, max_new_tokens + k + 1, None)
+            B, dev = tlogits.shape[0], tlogits.device
+            V = min(tlogits.shape[1], draft.lm_head.weight.shape[0])
+            book = AssistedBookkeeper(B, k, max_new_tokens, eos_token_id, eos_token_id if pad_token_id is None else pad_token_id)
+            nxt = K.row_argmax(tlogits[:, :V])
+            done = book.first(nxt).to(device=dev, dtype=torch.int32).contiguous()
+            lt_h, ld_h = tcache.lens.cpu().long(), dcache.lens.cpu().long()         # host copies of the caches' lens at round start
+            emb_t, emb_d = self.model.embed_tokens.weight, draft.model.embed_tokens.weight
+            d_first = None
+            trace = getattr(self, "assisted_trace", None)          # measurement only: a list that receives 5 events per round
+            mark = (lambda: None) if trace is None else (lambda: (ev.append(torch.cuda.Event(enable_timing=True)), ev[-1].record()))
+            while not book.finished:
+                ev = []
+                mark()
+                # the draft's decode steps append by an unchecked indexed copy: make room first (k steps, then a catch-up of <= 2)
+                if int(ld_h.max()) + k + 2 > dcache.smax:
+                    dcache.grow(int(ld_h.max()) + k + 2 + max_new_tokens)
+                tok, drafts = (nxt, []) if d_first is None else (d_first, [d_first])
+                while len(drafts) < k:
+                    tok = K.row_argmax(draft._decode_step(tok, dcache)[:, :V])
+                    drafts.append(tok)
+                draft_t = torch.stack(drafts, 1).contiguous()
+                mark()
+                chunk = torch.cat([nxt[:, None], draft_t], 1).reshape(-1).contiguous()
+                hid = self.model.forward_append(K.gather_rows(emb_t, None, chunk, emb_t.shape[1]), tcache, k + 1, max_len=int(lt_h.max()))
+                target = K.row_argmax(ops.linear_fwd(hid, self.head())[:, :V]).view(B, k + 1)
+                mark()
+                if getattr(self, "assisted_force_accept", False):                   # measurement only: every draft counts as accepted
+                    target[:, :k] = draft_t
+                pad = book.pad
+                block, nxt = K.spec_accept(draft_t, target, done, eos_token_id, pad, tcache.lens, dcache.lens)
+                blk = block.cpu()                                                   # the round's one read-back
+                book.update(blk)
+                n_acc = blk[:, k + 1].long()
+                mark()
+                if book.finished:
+                    break
+                # a sample the host stopped (max_new_tokens) is done on the device too: it emits nothing and, like an EOS row,
+                # advances one position per round while the others finish
+                done.copy_(book.stopped.to(torch.int32))
+                full = n_acc == k
+                # everything the catch-up needs is known from the block: no second read-back
+                idx = torch.tensor([2 * b + j for b in range(B) for j in ((0, 1) if bool(full[b]) else (1,))], dtype=torch.long)
+                toks = torch.stack([draft_t[:, k - 1], nxt], 1).reshape(-1)[idx.to(dev)].contiguous()
+                n_ch = 1 + full.to(torch.int32)
+                hid = draft.model.forward_append(K.gather_rows(emb_d, None, toks, emb_d.shape[1]), dcache, n_ch.to(dev), T=2,
+                                                 max_len=int((ld_h + torch.clamp(n_acc + 1, max=k)).max()))
+                lt_h, ld_h = lt_h + n_acc + 1, ld_h + n_acc + 1
+                last = (n_ch.cumsum(0) - 1).to(torch.int32).to(dev)
+                hl = K.gather_rows(hid, None, last, hid.shape[1])
+                d_first = K.row_argmax(ops.linear_fwd(hl, draft.head())[:, :V])
+                mark()
+                if trace is not None:
+                    trace.append(ev)
+        finally:
+            self.train(modes[0]), draft.train(modes[1])
+        seq = book.sequences().to(dev)
+        if return_dict_in_generate:
+            return AssistedOutput(seq, book.num_rounds, 1 + book.num_rounds, book.num_accepted.to(dev), tcache)
         return seq
 
     @torch.no_grad()
     def _beam_generate(self, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, do_sample, num_beams,
-                       num_return_sequences, length_penalty, early_stopping, return_dict_in_generate):
+                       num_return_sequences, length_penalty, early_stopping, return_dict_in_generate, past=None):
         """Beam search (HF `_beam_search`, do_sample=False; the bookkeeping and where it follows transformers 5.x rather than
         4.37: llavamod/generation.py).  The prompt is prefilled once at B rows and its cache replicated into B*num_beams rows
         (smax = S + max_new_tokens); every step is lmod_beam_topk_bf16 (top 2*nb candidates per sample, on the device) -> one
@@ -348,7 +521,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         was_training = self.training
         self.eval()                            # the MoE student routes with eval_capacity_factor, as greedy / sampling do
         try:
-            pcache, logits = self._prefill(input_ids, attention_mask, images, max_new_tokens)
+            pcache, logits = self._start(input_ids, attention_mask, images, max_new_tokens, past)
             B, nb, dev = logits.shape[0], num_beams, logits.device
             cfg = self.config
             cache = KVCache(cfg.num_hidden_layers, B * nb, pcache.smax, cfg.num_key_value_heads * cfg.head_dim, dev)
@@ -372,7 +545,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         finally:
             self.train(was_training)
         seq, scores = seq.to(dev), scores.to(dev)
-        return BeamSearchOutput(seq, scores) if return_dict_in_generate else seq
+        return BeamSearchOutput(seq, scores, cache) if return_dict_in_generate else seq
 
     # ---- checkpoints in the reference's layout -----------------------------------------------------------------------
     def save_config(self, save_directory):

@@ -74,6 +74,18 @@ class KVCache:
     def tensors(self):
         return self.k + self.v
 
+    def grow(self, smax):
+        """Reallocate for `smax` positions per sample, keeping [0, lens): new buffers, then ONE kv_gather_rows with the identity row
+        map over every layer's K and V.  A continuation that would run past the cache grows it instead of raising."""
+        if smax <= self.smax:
+            return
+        old = self.tensors()
+        B, _, width = old[0].shape
+        new = [torch.zeros((B, smax, width), device=t.device, dtype=BF16) for t in old]
+        K.kv_gather_rows(new, old, torch.arange(B, device=self.lens.device, dtype=torch.int32), self.lens)
+        n = len(self.k)
+        self.k, self.v, self.smax, self._alt = new[:n], new[n:], smax, None
+
     def reorder(self, src_row):
         """Beam search: row r takes row src_row[r]'s cached positions [0, lens[r]) (device int32 [B]).  One kv_gather_rows launch
         into the alternate buffers, which then become k / v (a gather by a permutation is not safe in place)."""
@@ -135,6 +147,21 @@ class Qwen2Attention(nn.Module):
         kc[bi, rt.pos_long] = qkv[:, nh * hd:(nh + nkv) * hd]                    # append (indexed copy, no arithmetic)
         vc[bi, rt.pos_long] = qkv[:, (nh + nkv) * hd:]
         o = K.attn_decode(qkv[:, :nh * hd], kc, vc, rt.lens_after, nh, nkv, hd, 1.0 / math.sqrt(hd))
+        return ops.linear_fwd(o, self._o.ensure())
+
+    def forward_append(self, x, rt):
+        """A chunk of new tokens per sample against the cache: x [R, H] packed live rows -> [R, H] (no autograd).  Exactly
+        forward_decode's projection + RoPE (linear_fwd, then rope_ at positions rt.pos = lens_before + t; at these row counts the
+        fused QKV+RoPE GEMM is never the library's choice, and it is bit-identical to this pair), one lmod_kv_append_rows for K and
+        V, then lmod_attn_append over all of a sample's rows at once.  Layer 0's V rows equal the decode path's bit for bit (same
+        GEMM, same input rows); from layer 1 on the inputs have passed an attention kernel with another summation order, so no
+        deeper K / V can be bit-equal whatever the GEMM does with M — they agree within rounding."""
+        nh, nkv, hd = self.nh, self.nkv, self.hd
+        qkv = ops.linear_fwd(x, self._qkv.ensure())
+        K.rope_(qkv, rt.cos, rt.sin, rt.pos, nh + nkv, hd)
+        kc, vc = rt.cache.k[rt.layer], rt.cache.v[rt.layer]
+        K.kv_append_rows(qkv, nh * hd, (nh + nkv) * hd, nkv * hd, kc, vc, rt.lens_before, rt.T, rt.max_len_after, cu_new=rt.cu)
+        o = K.attn_append(qkv[:, :nh * hd], kc, vc, rt.lens_after, nh, nkv, hd, 1.0 / math.sqrt(hd), rt.T, cu_new=rt.cu)
         return ops.linear_fwd(o, self._o.ensure())
 
 
@@ -202,6 +229,17 @@ class Qwen2DecoderLayer(nn.Module):
             m = m[0]
         return m, h2
 
+    def forward_append(self, delta, res, rt):
+        """forward_decode over the packed live rows of a chunk: only they enter the layer, so a MoE layer routes exactly the live
+        tokens and padded positions take no expert capacity."""
+        n1, _, h = K.rmsnorm_fwd(delta, self.input_layernorm.weight, self.input_layernorm.variance_epsilon, res=res)
+        a = self.self_attn.forward_append(n1, rt)
+        n2, _, h2 = K.rmsnorm_fwd(a, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon, res=h)
+        m = self.mlp(n2, rt)
+        if isinstance(m, tuple):
+            m = m[0]
+        return m, h2
+
     def forward_rows(self, delta, res, rt, rows, inv_rows):
         """Same layer, but everything after the attention core runs only on token rows `rows` (int32 [R]; inv_rows[t] =
         position of t in rows or -1): the LAST layer of a model whose consumer reads R << T rows (the loss rows).  The
@@ -261,6 +299,48 @@ class Qwen2Model(nn.Module):
                 delta, res = layer.forward_decode(delta, res, rt)
             y, _, _ = K.rmsnorm_fwd(delta, self.norm.weight, self.norm.variance_epsilon, res=res)
         cache.lens += 1
+        return y
+
+    def forward_append(self, inputs_embeds, cache, n_new, T=None, max_len=None):
+        """inputs_embeds [R, H]: the embeddings of the packed live rows of a chunk, sample-major.  n_new: an int (every sample brings
+        exactly that many tokens, R = B * n_new) or a device int32 [B] with 0 <= n_new[b] <= T (ragged; T required; a sample with 0
+        brings no row and keeps its cache as it is).  Appends to
+        `cache` (growing it if the chunk would run past smax) and returns the final-normed hidden states [R, H].  max_len: the
+        caller's upper bound of cache.lens when it has one (saves the read-back of lens.max())."""
+        dev = inputs_embeds.device
+        R, B = inputs_embeds.shape[0], cache.lens.shape[0]
+        ragged = torch.is_tensor(n_new)
+        T = int(n_new) if not ragged else int(T)
+        if not 1 <= T <= K.APPEND_T_MAX:
+            raise ValueError(f"a chunk holds 1..{K.APPEND_T_MAX} tokens per sample, got {T}")
+        if not ragged and R != B * T:
+            raise ValueError(f"{R} rows for {B} samples x {T} tokens")
+        hi = (int(cache.lens.max()) if max_len is None else int(max_len)) + T
+        if hi > cache.smax:
+            cache.grow(hi)
+        lens_before = cache.lens.clone()
+        if ragged:
+            n_new = n_new.to(device=dev, dtype=torch.int32)
+            cu = torch.zeros(B + 1, device=dev, dtype=torch.int32)
+            cu[1:] = n_new.cumsum(0)
+            seg = torch.repeat_interleave(torch.arange(B, device=dev), n_new.long(), output_size=R)
+            pos = (lens_before[seg] + (torch.arange(R, device=dev, dtype=torch.int32) - cu[seg])).to(torch.int32).contiguous()
+            lens_after = lens_before + n_new
+        else:
+            cu = None
+            pos = (lens_before[:, None] + torch.arange(T, device=dev, dtype=torch.int32)[None, :]).reshape(-1).contiguous()
+            lens_after = lens_before + T
+        cos, sin = rope_tables(self.config.head_dim, max(self.config.max_position_embeddings, cache.smax),
+                               self.config.rope_theta, dev)
+        rt = SimpleNamespace(B=B, S=T, T=T, cos=cos, sin=sin, pos=pos, seqlens=None, cache=cache, layer=0, cu=cu,
+                             lens_before=lens_before, lens_after=lens_after, max_len_after=hi)
+        delta, res = inputs_embeds, None
+        with torch.no_grad():
+            for i, layer in enumerate(self.layers):
+                rt.layer = i
+                delta, res = layer.forward_append(delta, res, rt)
+            y, _, _ = K.rmsnorm_fwd(delta, self.norm.weight, self.norm.variance_epsilon, res=res)
+        cache.lens.copy_(lens_after)
         return y
 
     def forward(self, inputs_embeds, B, S, seqlens=None, out_rows=None, inv_rows=None, cache=None, cu=None, pos=None):

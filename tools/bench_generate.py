@@ -12,6 +12,18 @@ floor either can reach.
     python tools/bench_generate.py --only 1x4 --reps 1   # one configuration (for a rocprofv3 --kernel-trace --stats run)
     python tools/bench_generate.py --only 1x1,8x1 --sample          # greedy lines + the sampling A/B
     python tools/bench_generate.py --only none --sample --sample-only 1 --device-arm-only --reps 1   # B = 1 device arm (trace)
+
+--append T (comma-separated list) times the multi-token cache extension against the decode path in the same process, the arms
+alternating call by call, over a 700-position cache: (a) lmod_attn_append for T queries of one sample against T calls of
+lmod_attn_decode at the same cache length — wrapper calls back to back over ONE cache that stays in L2 / Infinity Cache, launch
+overhead included: a warm-cache call cost, not the kernel time inside generate() (profiles/sample_kernel_trace.md has that); (b) one chunk forward of T tokens at B 1 (Qwen2Model.forward_append + lm_head) against one
+decode step at batch T.  --assistant k times greedy assisted generation: the teacher drafting for itself (every draft accepted: the
+mechanics' cost), the random-weight student drafting (nearly nothing accepted: the worst-case overhead) and the student with
+acceptance forced (the round's cost at full acceptance), against plain greedy; every round is also split into draft / verify /
+accept / catch-up by events inside the loop (model.assisted_trace).
+
+    python tools/bench_generate.py --only none --append 2,4,8 > profiles/append_attn.jsonl
+    python tools/bench_generate.py --only none --assistant 4 > profiles/assisted_generate.jsonl
 """
 import argparse
 import json
@@ -49,6 +61,122 @@ def timed(model, pr, nb, n_new, sample=None):
     return e0.elapsed_time(e1)
 
 
+def _ms(fn, reps):
+    """Device time of fn() per call: `reps` calls between two events."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def append_arms(model, Ts, text_len, reps):
+    import math
+    from llavamod import kernels as K
+    from llavamod import ops
+    cfg = model.config
+    nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+    scale, L = 1.0 / math.sqrt(hd), text_len - 1 + 576
+    g = torch.Generator().manual_seed(0)
+    for T in Ts:
+        # (a) the attention kernels alone: one sample, L cached positions (the chunk's own keys included)
+        q = torch.randn(T, nh * hd, generator=g).to(torch.bfloat16).cuda()
+        kc = torch.randn(1, L + 8, nkv * hd, generator=g).to(torch.bfloat16).cuda()
+        vc = torch.randn(1, L + 8, nkv * hd, generator=g).to(torch.bfloat16).cuda()
+        lens = torch.full((1,), L, dtype=torch.int32, device="cuda")
+        arms = {"append": lambda: K.attn_append(q, kc, vc, lens, nh, nkv, hd, scale, T),
+                "decode_x_T": lambda: [K.attn_decode(q[t:t + 1], kc, vc, lens, nh, nkv, hd, scale) for t in range(T)]}
+        res = {k: [] for k in arms}
+        for rep in range(reps + 1):                               # rep 0 warms both arms
+            for k, fn in arms.items():
+                ms = _ms(fn, 50)
+                if rep:
+                    res[k].append(ms)
+        print(json.dumps({"metric": "attn_append_vs_T_decode_calls_us", "T": T, "cache_positions": L, "nh": nh, "nkv": nkv, "hd": hd,
+                          "nsplit": K.attn_append_nsplit(1, nkv, L + 8), "append_us": round(1e3 * min(res["append"]), 2),
+                          "decode_x_T_us": round(1e3 * min(res["decode_x_T"]), 2),
+                          "append_us_all": [round(1e3 * v, 2) for v in res["append"]],
+                          "decode_x_T_us_all": [round(1e3 * v, 2) for v in res["decode_x_T"]]}), flush=True)
+        # (b) the model: a chunk of T tokens at B 1 against one decode step at batch T, caches of L positions
+        c1, _ = model._prefill(**{k: v[:1] for k, v in prompts(1, text_len).items()}, max_new_tokens=T + 1)
+        cT, _ = model._prefill(**prompts(T, text_len), max_new_tokens=2)
+        l1, lT = c1.lens.clone(), cT.lens.clone()
+        tok = torch.randint(0, 151643, (T,), generator=g).to(torch.int32).cuda()
+        emb_w = model.model.embed_tokens.weight
+
+        def chunk():
+            c1.lens.copy_(l1)
+            emb = K.gather_rows(emb_w, None, tok, emb_w.shape[1])
+            return ops.linear_fwd(model.model.forward_append(emb, c1, T, max_len=L), model.head())
+
+        def decode():
+            cT.lens.copy_(lT)
+            return model._decode_step(tok, cT)
+
+        arms = {"chunk_B1": chunk, "decode_batch_T": decode}
+        res = {k: [] for k in arms}
+        for rep in range(reps + 1):
+            for k, fn in arms.items():
+                ms = _ms(fn, 5)
+                if rep:
+                    res[k].append(ms)
+        a, b = min(res["chunk_B1"]), min(res["decode_batch_T"])
+        print(json.dumps({"metric": "chunk_forward_vs_decode_step_ms", "T": T, "cache_positions": L, "chunk_B1_ms": round(a, 3),
+                          "decode_batch_T_ms": round(b, 3), "ratio": round(a / b, 3),
+                          "chunk_B1_ms_all": [round(v, 3) for v in res["chunk_B1"]],
+                          "decode_batch_T_ms_all": [round(v, 3) for v in res["decode_batch_T"]]}), flush=True)
+        del c1, cT
+
+
+def assisted_arms(model, k, text_len, reps, n_new=33):
+    """ms per emitted token of plain greedy, of the teacher drafting for itself and of a random-weight student drafting, B 1."""
+    from bench import moe_model_args, student_cfg
+    from llavamod.model import LLaVAMoDQwen2ForCausalLM
+    student = LLaVAMoDQwen2ForCausalLM(student_cfg(4), device="cuda")
+    student.initialize_moe_modules(moe_model_args(4))
+    student.eval()
+    pr = prompts(1, text_len)
+
+    def run(draft):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        kw = {} if draft is None else dict(assistant_model=draft, num_assistant_tokens=k, return_dict_in_generate=True)
+        e0.record()
+        out = model.generate(**pr, max_new_tokens=n_new, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    # student_forced: the student drafts and every draft counts as accepted (model.assisted_force_accept, measurement only): the
+    # cost of a round at full acceptance with the real draft's cost; its tokens are not the teacher's greedy tokens
+    arms = {"greedy": (None, False), "self_draft": (model, False), "student_draft": (student, False), "student_forced": (student, True)}
+    res, stats, phases = {a: [] for a in arms}, {}, {}
+    for rep in range(reps + 1):
+        for a, (d, forced) in arms.items():
+            model.assisted_force_accept = forced
+            model.assisted_trace = [] if d is not None else None
+            ms, out = run(d)
+            if rep:
+                res[a].append(ms)
+            if d is not None:
+                stats[a] = dict(rounds=out.num_rounds, accepted=int(out.num_accepted.sum()), tokens=int(out.sequences.shape[1]))
+                full = [ev for ev in model.assisted_trace if len(ev) == 5]        # the last round ends before the catch-up
+                names = ("draft", "verify", "accept", "catchup")
+                phases[a] = {n: round(sum(ev[i].elapsed_time(ev[i + 1]) for ev in full) / max(1, len(full)), 3)
+                             for i, n in enumerate(names)}
+    del model.assisted_force_accept, model.assisted_trace
+    # the prefill(s) are inside the per-call figures; the per-round phases are device time between events recorded inside the loop
+    # (accept includes the round's one read-back and the host bookkeeping)
+    rec = {"metric": "assisted_generate_ms_per_call", "B": 1, "k": k, "new_tokens": n_new, "prompt_positions": text_len - 1 + 576}
+    for a in arms:
+        rec[f"{a}_ms"] = round(min(res[a]), 2)
+        rec[f"{a}_ms_all"] = [round(v, 2) for v in res[a]]
+    rec.update({f"{a}_{n}": v for a, st in stats.items() for n, v in st.items()})
+    rec.update({f"{a}_round_ms": ph for a, ph in phases.items()})
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--text-len", type=int, default=125, help="text tokens incl. the image placeholder (+575 -> prompt length)")
@@ -59,6 +187,8 @@ def main():
     ap.add_argument("--sample", action="store_true", help="also time the sampling arms, device kernel against the torch path")
     ap.add_argument("--sample-only", default=None, help="comma-separated B of the sampling arms (default 1,8)")
     ap.add_argument("--device-arm-only", action="store_true", help="sampling: skip the torch arm (for a kernel trace)")
+    ap.add_argument("--append", default=None, help="comma-separated chunk lengths T: chunk path against the decode path")
+    ap.add_argument("--assistant", type=int, default=None, help="k: assisted generation (self-draft, student draft) against greedy")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate.py measures on the GPU"
     from bench import teacher_cfg
@@ -79,6 +209,10 @@ def main():
                           "prompt_positions": a.text_len - 1 + 576, "ms_per_token": round(min(per), 3),
                           "ms_per_token_all": [round(p, 3) for p in per], "ms_call_n1": [round(x, 1) for x in t1],
                           "ms_call_n2": [round(y, 1) for y in t2], "n1": a.n1, "n2": a.n2}), flush=True)
+    if a.append:
+        append_arms(model, [int(x) for x in a.append.split(",")], a.text_len, a.reps)
+    if a.assistant:
+        assisted_arms(model, a.assistant, a.text_len, a.reps)
     if not a.sample:
         return
     arms = (True,) if a.device_arm_only else (True, False)
