@@ -317,6 +317,30 @@ int lmod_kv_gather_rows(void* const* dst, const void* const* src, int ntensor, c
 int lmod_sample_bf16(const void* logits, long long ld, int V, const float* u, int R, float temperature, int top_k, float top_p,
                      int chunk, void* ws, long long ws_bytes, int* out_token, float* out_stats, hipStream_t stream);
 
+/* ---- logits processors and stop sequences (generate(repetition_penalty / no_repeat_ngram_size / bad_words_ids / suppress_tokens /
+ *      min_new_tokens / stop_sequences); HF GenerationMixin semantics, transformers 5.x) ----------------------------------------
+ * Shared state, all int32 and caller-owned: hist [R, ld_hist] (a row's live prompt ids followed by what it has generated),
+ *   n_hist [R] (tokens in the row), n_prompt [R] (how many of them are prompt), n_gen [R] = n_hist - n_prompt, done [R].  A table of
+ *   token sequences is `flat` (all tokens back to back) and `off` [n + 1] (sequence e is flat[off[e] .. off[e+1])).
+ * lmod_logits_process_bf16: edits logits [R, ld] bf16 (V live columns) in place, one workgroup per row, in this order (barriers
+ *   between the phases): (1) penalty != 1: every DISTINCT history token t gets x = x < 0 ? x * penalty : x / penalty once (fp32 on
+ *   the bf16 value, IEEE multiply / divide, one round-to-nearest-even to bf16); first occurrences are found with a V-bit bitmap in
+ *   LDS: LMOD_EUNSUPPORTED when V > 524288 (64 KB of LDS) and penalty != 1.  (2) ngram = n > 0 and n_hist >= n: the last token of
+ *   every history window of n tokens whose first n-1 tokens equal the history's last n-1 tokens is banned (n = 1: every token seen).
+ *   (3) the bad-word table: a one-token entry is banned always, a longer entry's last token when n_hist >= its length and the
+ *   history ends with its other tokens.  (4) eos >= 0 and n_gen < min_new: eos is banned.  A ban stores bf16 -inf.  History ids
+ *   are compared as plain integers; an id outside [0, V) (the negative image placeholder) is never penalised or banned.  Elements
+ *   that no phase touches are not written.  penalty > 0.
+ * lmod_gen_push_stop: one step's bookkeeping.  A done row's token becomes `pad`.  A live row's token is appended to hist
+ *   (n_hist and n_gen advance; the caller keeps n_hist < ld_hist: a full row is left as it is); done[r] is set when the token is
+ *   eos (eos >= 0) or when the row's last len tokens equal a stop sequence of length len and all of them were generated
+ *   (n_hist - len >= n_prompt): a match that needs a prompt token does not count. */
+int lmod_logits_process_bf16(void* logits, long long ld, int V, int R, const int* hist, int ld_hist, const int* n_hist,
+                             const int* n_gen, float penalty, int ngram, const int* bad_flat, const int* bad_off, int n_bad,
+                             int min_new, int eos, hipStream_t stream);
+int lmod_gen_push_stop(int* tokens, int* done, int* hist, int ld_hist, int* n_hist, const int* n_prompt, int* n_gen, int eos,
+                       int pad, const int* stop_flat, const int* stop_off, int n_stop, int R, hipStream_t stream);
+
 /* ---- sparse MoE (DeepSpeed 0.9.5 TopKGate/top1gating/top2gating/MOELayer semantics) ------------
  * logits[T,E] = x.float() @ wg^T  (TopKGate.forward; wg kept fp32).
  * Experts per layer: 1 <= E <= 32 (`--num_experts`, config/args.py:46); the per-token kernels are instantiated for

@@ -58,6 +58,8 @@ SIGNATURES = {
     "lmod_beam_topk_bf16": "pqi" + "p" + "iii" + "pq" + "ppp" + "p",
     "lmod_kv_gather_rows": "pp" + "i" + "pp" + "iiiii" + "p",
     "lmod_sample_bf16": "pqi" + "pi" + "fif" + "i" + "pq" + "pp" + "p",
+    "lmod_logits_process_bf16": "pqii" + "pipp" + "fi" + "ppi" + "ii" + "p",
+    "lmod_gen_push_stop": "pp" + "pipp" + "p" + "ii" + "ppi" + "i" + "p",
     "lmod_moe_router_fwd": "ppp" + "iii" + "p",
     "lmod_moe_gate": "pp" + "iiii" + "pppppppppppppp" + "iQQp" + "p",
     "lmod_moe_combine_fwd": "pppppp" + "ii" + "p",

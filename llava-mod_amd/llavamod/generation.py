@@ -278,3 +278,114 @@ class AssistedBookkeeper:
 
     def sequences(self):
         return self.seq[:, :int(self.n.max())]
+
+
+# ---------------------------------------------------------------------------------------------- logits processors, stop sequences
+class LogitsPlan:
+    """What `check_logits_args` made of generate()'s processing arguments: penalty (float), ngram (int), bad (the combined table of
+    bad_words_ids and suppress_tokens: a list of token lists), min_new (int, 0 without an eos_token_id), stops (stop_sequences
+    followed by the keyword sequences of stopping_criteria).  `process`: a logits kernel has to run every step."""
+
+    def __init__(self, penalty, ngram, bad, min_new, stops):
+        self.penalty, self.ngram, self.bad, self.min_new, self.stops = penalty, ngram, bad, min_new, stops
+        self.process = penalty != 1.0 or ngram > 0 or bool(bad) or min_new > 0
+
+
+def _token_seqs(name, seqs, vocab_size):
+    if isinstance(seqs, (str, bytes)) or not hasattr(seqs, "__iter__"):
+        raise ValueError(f"{name} must be a list of token-id lists, got {seqs!r}")
+    out = []
+    for s in seqs:
+        s = s.tolist() if hasattr(s, "tolist") else s
+        if isinstance(s, (str, bytes)) or not hasattr(s, "__iter__"):
+            raise ValueError(f"{name} must be a list of token-id lists, got the element {s!r}")
+        s = list(s)
+        if not s:
+            raise ValueError(f"{name} holds an empty sequence")
+        for t in s:
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < vocab_size:
+                raise ValueError(f"{name}: token id {t!r} is not an int in [0, {vocab_size})")
+        out.append(s)
+    return out
+
+
+def check_logits_args(repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0,
+                      stop_sequences=None, stopping_criteria=None, eos_token_id=None, vocab_size=None, num_beams=1,
+                      assistant_model=None):
+    """The logits-processing and stop arguments of `generate()` (HF names and semantics).  Returns None when every one of them is at
+    its default — the caller then runs exactly the path it ran before these arguments existed — and a `LogitsPlan` otherwise.
+    Raises before anything is launched: ValueError for a value out of range, a table over the kernels' limits (kernels.LOGITS_MAX_SEQS
+    sequences per table, kernels.LOGITS_MAX_SEQ_LEN tokens per sequence), a token id outside [0, vocab_size), or any of these
+    arguments combined with num_beams > 1 or assistant_model (HF processes log-softmaxed scores there; not built); TypeError for a
+    stopping criterion without `keyword_ids`.
+
+    stopping_criteria: each element must expose `keyword_ids`, an iterable of 1-D int tensors or lists — what the reference's
+    KeywordsStoppingCriteria (mm_utils.py:74-105) builds in its __init__; its sequences join stop_sequences.  Only that token-level
+    test is reproduced: the class's string-level fallback (decode the tail, then search the keyword as a substring) is not, and
+    neither is its `all(...)` over the batch — stopping is per row, like EOS."""
+    from .kernels import LOGITS_MAX_SEQ_LEN, LOGITS_MAX_SEQS
+    given = {"repetition_penalty": repetition_penalty != 1.0, "no_repeat_ngram_size": no_repeat_ngram_size != 0,
+             "bad_words_ids": bad_words_ids is not None, "suppress_tokens": suppress_tokens is not None,
+             "min_new_tokens": min_new_tokens != 0, "stop_sequences": stop_sequences is not None,
+             "stopping_criteria": stopping_criteria is not None}
+    used = [k for k, v in given.items() if v]
+    if not used:
+        return None
+    if num_beams != 1:
+        raise ValueError(f"{', '.join(used)} cannot be combined with num_beams > 1: beam search scores log-softmaxed logits, which "
+                         "these processors do not reach yet")
+    if assistant_model is not None:
+        raise ValueError(f"{', '.join(used)} cannot be combined with assistant_model: assisted decoding verifies unprocessed logits")
+    if vocab_size is None:
+        raise ValueError("vocab_size is needed to check token ids")
+    p = repetition_penalty
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not p > 0:
+        raise ValueError(f"repetition_penalty must be a number > 0, got {p!r}")
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name} must be an int >= 0, got {v!r}")
+    bad = _token_seqs("bad_words_ids", bad_words_ids, vocab_size) if bad_words_ids is not None else []
+    if eos_token_id is not None:
+        bad = [s for s in bad if s != [int(eos_token_id)]]                 # HF's NoBadWordsLogitsProcessor drops it too
+    if suppress_tokens is not None:
+        bad += _token_seqs("suppress_tokens", [[t] for t in (suppress_tokens.tolist() if hasattr(suppress_tokens, "tolist")
+                                                               else suppress_tokens)], vocab_size)
+    stops = _token_seqs("stop_sequences", stop_sequences, vocab_size) if stop_sequences is not None else []
+    if stopping_criteria is not None:
+        for c in stopping_criteria:
+            if not hasattr(c, "keyword_ids"):
+                raise TypeError(f"stopping_criteria: only token-level keyword criteria are supported (an object with `keyword_ids`, "
+                                f"as the reference's KeywordsStoppingCriteria), got {type(c).__name__}")
+            stops += _token_seqs("stopping_criteria keyword_ids", c.keyword_ids, vocab_size)
+    for name, table in (("bad_words_ids + suppress_tokens", bad), ("stop_sequences + stopping_criteria", stops)):
+        if len(table) > LOGITS_MAX_SEQS:
+            raise ValueError(f"{name}: {len(table)} sequences, at most {LOGITS_MAX_SEQS} are supported")
+        longest = max((len(s) for s in table), default=0)
+        if longest > LOGITS_MAX_SEQ_LEN:
+            raise ValueError(f"{name}: a sequence of {longest} tokens, at most {LOGITS_MAX_SEQ_LEN} are supported")
+    return LogitsPlan(float(p), int(no_repeat_ngram_size), bad, int(min_new_tokens) if eos_token_id is not None else 0, stops)
+
+
+def gen_push_stop(tokens, done, hist, n_hist, n_prompt, n_gen, eos, pad, stops):
+    """One generation step's bookkeeping in plain torch — what lmod_gen_push_stop computes on the device (the product path calls the
+    kernel; this is the statement the tests hold both against).  tokens [R], done [R], hist [R, L], n_hist / n_prompt / n_gen [R];
+    eos None: no stop token; stops: a list of token lists.  A done row's token becomes pad.  A live row's token is appended to its
+    history; the row is done when the token is eos, or when its history now ends with a stop sequence that lies entirely behind the
+    prompt (n_hist - len >= n_prompt).  Returns new (tokens, done, hist, n_hist, n_gen) without modifying its inputs."""
+    was = done.bool()
+    live = ~was
+    tokens = torch.where(was, torch.full_like(tokens, 0 if pad is None else int(pad)), tokens)
+    hist, R = hist.clone(), tokens.shape[0]
+    rows = torch.arange(R, device=tokens.device)[live]
+    hist[rows, n_hist.long()[live]] = tokens[live].to(hist.dtype)
+    n_hist, n_gen = n_hist + live.to(n_hist.dtype), n_gen + live.to(n_gen.dtype)
+    fin = was.clone()
+    if eos is not None:
+        fin |= live & (tokens == int(eos))
+    for s in stops or ():
+        k = len(s)
+        fits = live & (n_hist.long() - k >= n_prompt.long())
+        idx = (n_hist.long()[:, None] - k + torch.arange(k, device=tokens.device)[None, :]).clamp_min(0)
+        tail = hist.gather(1, idx).long()
+        fin |= fits & (tail == torch.tensor(s, device=tokens.device)[None, :]).all(1)
+    return tokens, fin.to(done.dtype), hist, n_hist, n_gen

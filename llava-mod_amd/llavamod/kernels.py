@@ -524,6 +524,56 @@ def sample(logits, u, temperature=1.0, top_k=None, top_p=None, stats=False):
     return (tokens, st) if stats else tokens
 
 
+# ------------------------------------------------------------------------------------------ logits processors / stop sequences
+LOGITS_MAX_SEQS = 16          # sequences in the bad-word table, and in the stop table
+LOGITS_MAX_SEQ_LEN = 16       # tokens per sequence
+
+
+def seq_table(seqs, device):
+    """A list of token sequences as the device table the logits kernels read: (flat int32 [sum of lengths], off int32 [n + 1], n);
+    None for an empty list.  One host -> device copy."""
+    if not seqs:
+        return None
+    flat, off = [], [0]
+    for s in seqs:
+        flat.extend(int(t) for t in s)
+        off.append(len(flat))
+    both = torch.tensor(flat + off, dtype=torch.int32).to(device)
+    return both[:len(flat)], both[len(flat):], len(seqs)
+
+
+def logits_process_(logits, hist, n_hist, n_gen, penalty=1.0, ngram=0, bad=None, min_new=0, eos=None):
+    """In place on logits [R, V] bf16 (row stride may exceed V): repetition penalty, no-repeat n-gram bans, bad-word bans and the
+    min-new-tokens EOS ban from the history hist [R, L] / n_hist [R] / n_gen [R] (device int32), in HF's order
+    (lmod_logits_process_bf16 in include/lmod_hip.h).  bad: a `seq_table` or None.  Returns logits."""
+    R, V = logits.shape
+    assert logits.dtype == BF16 and logits.is_cuda and logits.stride(1) == 1
+    assert hist.dim() == 2 and hist.shape[0] == R and hist.stride(1) == 1
+    for t in (hist, n_hist, n_gen):
+        assert t.dtype == torch.int32 and t.is_cuda
+    assert n_hist.is_contiguous() and n_gen.is_contiguous() and n_hist.numel() == R and n_gen.numel() == R
+    bf, bo, nb = bad if bad is not None else (None, None, 0)
+    rc = call("lmod_logits_process_bf16", ptr(logits), logits.stride(0), V, R, ptr(hist), hist.stride(0), ptr(n_hist), ptr(n_gen),
+              float(penalty), int(ngram), ptr(bf), ptr(bo), nb, int(min_new), -1 if eos is None else int(eos),
+              allow=(_hip.UNSUPPORTED,))
+    if rc:
+        raise ValueError(f"repetition_penalty needs a {V}-bit first-occurrence bitmap in LDS: a vocabulary above 524288 is not supported")
+    return logits
+
+
+def gen_push_stop_(tokens, done, hist, n_hist, n_prompt, n_gen, eos, pad, stop=None):
+    """One generation step's bookkeeping on the device (lmod_gen_push_stop), everything int32 and updated in place: a done row's
+    token becomes pad; a live row's token is appended to its history and done is set on EOS or when the row's generated tokens end
+    with a sequence of the stop table (`seq_table` or None)."""
+    R = tokens.numel()
+    for t in (tokens, done, hist, n_hist, n_prompt, n_gen):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert hist.dim() == 2 and hist.shape[0] == R and all(t.numel() == R for t in (done, n_hist, n_prompt, n_gen))
+    sf, so, ns = stop if stop is not None else (None, None, 0)
+    call("lmod_gen_push_stop", ptr(tokens), ptr(done), ptr(hist), hist.shape[1], ptr(n_hist), ptr(n_prompt), ptr(n_gen),
+         -1 if eos is None else int(eos), 0 if pad is None else int(pad), ptr(sf), ptr(so), ns, R)
+
+
 # ------------------------------------------------------------------------------------------ MoE
 def moe_router_fwd(x, wg):
     T, H = x.shape

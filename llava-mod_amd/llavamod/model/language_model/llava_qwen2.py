@@ -337,7 +337,9 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
     def generate(self, input_ids=None, attention_mask=None, images=None, max_new_tokens=16, eos_token_id=None,
                  pad_token_id=None, do_sample=False, temperature=1.0, top_k=None, top_p=None, seed=None, num_beams=1,
                  num_return_sequences=1, length_penalty=1.0, early_stopping=False, return_dict_in_generate=False,
-                 past_key_values=None, assistant_model=None, num_assistant_tokens=5, **kwargs):
+                 past_key_values=None, assistant_model=None, num_assistant_tokens=5, repetition_penalty=1.0,
+                 no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0, stop_sequences=None,
+                 stopping_criteria=None, **kwargs):
         """Generation with a KV cache (the reference's eval path calls HF `generate` on the Eval model,
         llava_qwen2_moe.py:629-681; its serving code passes do_sample / temperature / top_p, its eval scripts num_beams).
         Greedy by default; do_sample=True draws from the temperature / top-k / top-p filtered distribution (`seed` makes the
@@ -358,7 +360,32 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         cannot be chained from without picking rows.  Assisted decoding: when max_new_tokens cuts a round short the target's cache
         holds accepted tokens behind the returned ones.
 
-        assistant_model (with num_assistant_tokens = k in 1..APPEND_T_MAX-1): greedy assisted decoding, `_assisted_generate`."""
+        assistant_model (with num_assistant_tokens = k in 1..APPEND_T_MAX-1): greedy assisted decoding, `_assisted_generate`.
+
+        Logits processors and stop sequences (HF names and semantics, transformers 5.x; greedy and sampling only — with
+        num_beams > 1 or assistant_model any of them raises ValueError), applied on the device every step by
+        lmod_logits_process_bf16, in this order, before the token is selected:
+          repetition_penalty (> 0): every distinct token of the row's history gets x = x * p if x < 0 else x / p, once;
+          no_repeat_ngram_size n: every token that would complete an n-gram already in the history is banned (n = 1: every token
+            seen; nothing while the history is shorter than n);
+          bad_words_ids (list of token lists) and suppress_tokens (list of ids = one-token bad words): a one-token entry is always
+            banned, a longer entry's last token when the history ends with the rest of the entry (and, as in HF, holds at least as
+            many tokens as the entry); an entry equal to [eos_token_id] is dropped;
+          min_new_tokens: eos_token_id is banned while the row has generated fewer tokens (ignored without an eos_token_id).
+        A ban sets the logit to -inf.  A row's history is its live `input_ids` of this call (the first attention_mask.sum()
+        positions, ids as given: the negative image placeholder is compared like any integer by the n-gram test and skipped by the
+        penalty and the bans) followed by what it has generated in this call; with num_return_sequences > 1 it is replicated as the
+        cache is.  stop_sequences (list of token lists): once a row's GENERATED tokens (never the prompt) end with one of them the row
+        is done — per row, like EOS: the stop tokens stay, later positions hold pad_token_id, the loop ends when every row is done
+        (lmod_gen_push_stop).  stopping_criteria: objects exposing `keyword_ids` (the reference's KeywordsStoppingCriteria); their
+        sequences join stop_sequences.  Only that token-level test is reproduced: the class's string-level fallback (decode, then
+        substring search) and its all() over the batch are not; anything else raises TypeError.  At most kernels.LOGITS_MAX_SEQS
+        sequences of at most kernels.LOGITS_MAX_SEQ_LEN tokens per table, ids in [0, V).  A call that uses none of these arguments
+        runs the loop below exactly as before."""
+        from ...generation import check_logits_args
+        lplan = check_logits_args(repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens,
+                                  stop_sequences, stopping_criteria, eos_token_id, self.lm_head.weight.shape[0], num_beams,
+                                  assistant_model)
         if assistant_model is not None:
             from ...generation import check_assisted_args
             check_assisted_args(do_sample, num_beams, num_assistant_tokens, K.APPEND_T_MAX, num_return_sequences)
@@ -370,6 +397,10 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                                        past_key_values)
         from ...generation import GreedyOutput, SampleOutput, check_sample_args
         check_sample_args(do_sample, temperature, top_k, top_p, num_return_sequences)
+        if lplan is not None:
+            return self._processed_generate(lplan, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id,
+                                            do_sample, temperature, top_k, top_p, seed, num_return_sequences,
+                                            return_dict_in_generate, past_key_values)
         n = num_return_sequences
         on_device = do_sample and self.sample_on_device
         was_training = self.training
@@ -418,6 +449,80 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                 break
             logits = self._decode_step(nxt, cache)
         self.train(was_training)
+        seq = torch.stack(out, 1)
+        if do_sample and return_dict_in_generate:
+            return SampleOutput(seq, torch.stack(lps, 1) if lps else None, cache)
+        return GreedyOutput(seq, cache) if return_dict_in_generate else seq
+
+    @torch.no_grad()
+    def _processed_generate(self, lplan, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, do_sample,
+                            temperature, top_k, top_p, seed, n, return_dict_in_generate, past):
+        """Greedy / sampling generate() with logits processors and stop sequences (`lplan`, generation.check_logits_args).  The
+        token history [rows, prompt + max_new_tokens], its counters and the done flags live on the device, allocated once; per
+        step: lmod_logits_process_bf16 in place on the step's logits (when a processor is active), the usual selection
+        (lmod_row_argmax_bf16 / lmod_sample_bf16), lmod_gen_push_stop (pad, history append, EOS and stop-sequence test), one
+        read-back of the done flags, one decode step.  `logits_glue` (measurement only, tools/bench_generate.py --processors): a
+        pair of torch functions (process, push) that stand in for the two kernels, the A/B baseline as `sample_on_device` is."""
+        from ...generation import GreedyOutput, SampleOutput
+        glue = getattr(self, "logits_glue", None)
+        on_device = do_sample and self.sample_on_device
+        was_training = self.training
+        self.eval()
+        try:
+            cache, logits = self._start(input_ids, attention_mask, images, max_new_tokens, past)
+            B, dev = logits.shape[0], logits.device
+            ids = input_ids.to(device=dev, dtype=torch.int32)
+            S = ids.shape[1]
+            n_prompt = (attention_mask.to(dev).to(torch.int32).sum(1).to(torch.int32) if attention_mask is not None
+                        else torch.full((B,), S, device=dev, dtype=torch.int32))
+            hist = torch.zeros((B, S + max_new_tokens), device=dev, dtype=torch.int32)
+            hist[:, :S] = ids
+            if n > 1:
+                cfg = self.config
+                pcache, cache = cache, KVCache(cfg.num_hidden_layers, B * n, cache.smax, cfg.num_key_value_heads * cfg.head_dim, dev)
+                cache.lens.copy_(pcache.lens.repeat_interleave(n))
+                K.kv_gather_rows(cache.tensors(), pcache.tensors(), torch.arange(B * n, device=dev, dtype=torch.int32) // n, cache.lens)
+                del pcache
+                logits, hist, n_prompt = logits.repeat_interleave(n, 0), hist.repeat_interleave(n, 0), n_prompt.repeat_interleave(n)
+                B = B * n
+            hist, n_prompt = hist.contiguous(), n_prompt.contiguous()
+            n_hist, n_gen = n_prompt.clone(), torch.zeros(B, device=dev, dtype=torch.int32)
+            done = torch.zeros(B, device=dev, dtype=torch.int32)
+            bad, stop = K.seq_table(lplan.bad, dev), K.seq_table(lplan.stops, dev)
+            pad = eos_token_id if pad_token_id is None else pad_token_id
+            can_stop = eos_token_id is not None or stop is not None
+            gen = None
+            if do_sample:
+                gen = torch.Generator(device=dev)
+                gen.manual_seed(int(seed) if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))   # as generate()
+            want_lp = on_device and return_dict_in_generate
+            out, lps = [], []
+            for step in range(max_new_tokens):
+                if lplan.process and glue is None:
+                    K.logits_process_(logits, hist, n_hist, n_gen, lplan.penalty, lplan.ngram, bad, lplan.min_new, eos_token_id)
+                elif lplan.process:
+                    logits = glue[0](logits, hist, n_hist, n_gen, penalty=lplan.penalty, ngram=lplan.ngram, bad=lplan.bad,
+                                     min_new=lplan.min_new, eos=eos_token_id)
+                if on_device:
+                    u = torch.rand(B, generator=gen, device=dev)
+                    nxt = K.sample(logits, u, temperature, top_k, top_p, stats=want_lp)
+                    if want_lp:
+                        nxt, st = nxt
+                        x = logits.gather(1, nxt.long()[:, None]).squeeze(1).double() / max(float(temperature), 1e-6)
+                        lp = (x - st[:, 0].double() - torch.log(st[:, 1].double())).clamp(max=0.0).float()
+                        lps.append(torch.where(done != 0, torch.zeros_like(lp), lp))
+                else:
+                    nxt = self._sample(logits, temperature, top_k, top_p, gen) if do_sample else K.row_argmax(logits)
+                if glue is None:
+                    K.gen_push_stop_(nxt, done, hist, n_hist, n_prompt, n_gen, eos_token_id, pad, stop)
+                else:
+                    nxt, done, hist, n_hist, n_gen = glue[1](nxt, done, hist, n_hist, n_prompt, n_gen, eos_token_id, pad, lplan.stops)
+                out.append(nxt.long())
+                if step + 1 == max_new_tokens or (can_stop and bool(done.all())):
+                    break
+                logits = self._decode_step(nxt, cache)
+        finally:
+            self.train(was_training)
         seq = torch.stack(out, 1)
         if do_sample and return_dict_in_generate:
             return SampleOutput(seq, torch.stack(lps, 1) if lps else None, cache)

@@ -24,6 +24,14 @@ accept / catch-up by events inside the loop (model.assisted_trace).
 
     python tools/bench_generate.py --only none --append 2,4,8 > profiles/append_attn.jsonl
     python tools/bench_generate.py --only none --assistant 4 > profiles/assisted_generate.jsonl
+
+--processors times greedy generate() with repetition_penalty=1.1, no_repeat_ngram_size=3 and one two-token stop sequence that never
+fires, B in {1, 8}, three arms alternating call by call in one process, best of --reps: plain greedy (none of the arguments: the
+loop without a history), the device kernels (lmod_logits_process_bf16 + lmod_gen_push_stop) and torch glue (the statements of
+tests/_logits_ref.py on device tensors, through model.logits_glue).  One JSON line per B.
+
+    python tools/bench_generate.py --only none --processors > profiles/logits_process_ab.jsonl
+    python tools/bench_generate.py --only none --processors --processors-only 1 --device-arm-only --reps 1   # B = 1 device arm (trace)
 """
 import argparse
 import json
@@ -177,6 +185,48 @@ def assisted_arms(model, k, text_len, reps, n_new=33):
     print(json.dumps(rec), flush=True)
 
 
+PROCESSORS = dict(repetition_penalty=1.1, no_repeat_ngram_size=3, stop_sequences=[[151640, 151641]])
+
+
+def processor_arms(model, Bs, text_len, reps, n1, n2, device_only=False):
+    """ms per new token of greedy generate(): plain, with the processors on the device kernels, with the processors as torch glue."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _logits_ref as LR
+
+    def run(pr, arm, n_new):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        if arm == "glue":
+            model.logits_glue = (LR.process_logits, LR.push_stop)
+        try:
+            e0.record()
+            out = model.generate(**pr, max_new_tokens=n_new, **({} if arm == "plain" else PROCESSORS))
+            e1.record()
+            torch.cuda.synchronize()
+        finally:
+            if arm == "glue":
+                del model.logits_glue
+        assert out.shape[1] == n_new, out.shape                    # the stop sequence never fires: every call runs its full length
+        return e0.elapsed_time(e1)
+
+    arms = ("device",) if device_only else ("plain", "device", "glue")
+    for B in Bs:
+        pr = prompts(B, text_len)
+        t1, t2 = {a: [] for a in arms}, {a: [] for a in arms}
+        for rep in range(reps + 1):                                # rep 0 warms every arm at both lengths
+            for a in arms:
+                x, y = run(pr, a, n1), run(pr, a, n2)
+                if rep:
+                    t1[a].append(x)
+                    t2[a].append(y)
+        rec = {"metric": "generate_processors_ms_per_new_token", "B": B, **PROCESSORS, "prompt_positions": text_len - 1 + 576,
+               "n1": n1, "n2": n2}
+        for a in arms:
+            per = [(y - x) / (n2 - n1) for x, y in zip(t1[a], t2[a])]
+            rec[f"ms_per_token_{a}"] = round(min(per), 3)
+            rec[f"ms_per_token_{a}_all"] = [round(v, 3) for v in per]
+        print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--text-len", type=int, default=125, help="text tokens incl. the image placeholder (+575 -> prompt length)")
@@ -189,6 +239,8 @@ def main():
     ap.add_argument("--device-arm-only", action="store_true", help="sampling: skip the torch arm (for a kernel trace)")
     ap.add_argument("--append", default=None, help="comma-separated chunk lengths T: chunk path against the decode path")
     ap.add_argument("--assistant", type=int, default=None, help="k: assisted generation (self-draft, student draft) against greedy")
+    ap.add_argument("--processors", action="store_true", help="greedy with logits processors: plain / device kernels / torch glue")
+    ap.add_argument("--processors-only", default=None, help="comma-separated B of the processor arms (default 1,8)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate.py measures on the GPU"
     from bench import teacher_cfg
@@ -213,6 +265,9 @@ def main():
         append_arms(model, [int(x) for x in a.append.split(",")], a.text_len, a.reps)
     if a.assistant:
         assisted_arms(model, a.assistant, a.text_len, a.reps)
+    if a.processors:
+        processor_arms(model, [int(x) for x in a.processors_only.split(",")] if a.processors_only else [1, 8], a.text_len, a.reps,
+                       a.n1, a.n2, a.device_arm_only)
     if not a.sample:
         return
     arms = (True,) if a.device_arm_only else (True, False)
