@@ -341,6 +341,31 @@ int lmod_logits_process_bf16(void* logits, long long ld, int V, int R, const int
 int lmod_gen_push_stop(int* tokens, int* done, int* hist, int ld_hist, int* n_hist, const int* n_prompt, int* n_gen, int eos,
                        int pad, const int* stop_flat, const int* stop_off, int n_stop, int R, hipStream_t stream);
 
+/* ---- continuous batching (generate_batch(): a finished slot of the running batch is refilled while the others keep decoding;
+ *      csrc/batch.hip) -------------------------------------------------------------------------------------------------------
+ * lmod_kv_admit_rows: the scatter that lmod_kv_gather_rows is not.  For every tensor t < ntensor (device tables dst[t] / src[t], 16-byte
+ *   aligned bf16 caches) dst[t][dst_row[r], 0:lens[r], :] = src[t][r, 0:lens[r], :], r < R; src [R, smax_src, width] is the temporary
+ *   cache an admission prefill wrote, dst [B, smax_dst, width] the slot cache; one launch covers all layers' K and V.  dst_row[r] in
+ *   [0, B), pairwise distinct: the host checks, the device trusts (a row outside [0, B) is skipped).  Rows of dst that dst_row does not
+ *   name and positions >= lens[r] of the named rows are not written.  width % 8 == 0.  max_len: the caller's upper bound of lens[r];
+ *   LMOD_EINVAL if it exceeds smax_dst or smax_src (grow the cache first) - the device never clamps a position (a row longer than
+ *   max_len is skipped), the rule of lmod_kv_append_rows.  dst and src must not overlap.  R == 0 is a no-op.
+ * lmod_slot_admit: re-arms the generation state of the admitted slots, one launch.  For s = dst_row[r], r < R (s in [0, B), distinct):
+ *   hist[s, 0:n_prompt_new[r]] = prompt_ids[r, 0:n_prompt_new[r]] (prompt_ids [R, ld_prompt]; the rest of the history row stays as it
+ *   is: it is dead behind n_hist), n_prompt[s] = n_hist[s] = n_prompt_new[r], n_gen[s] = 0, done[s] = 0, cache_lens[s] = lens_new[r],
+ *   req_id[s] = req_new[r].  hist / n_hist / n_prompt / n_gen / done are the arrays of lmod_logits_process_bf16 and lmod_gen_push_stop,
+ *   cache_lens the slot cache's lens, req_id [B] the request each slot serves.  0 <= n_prompt_new[r] <= min(ld_prompt, ld_hist) (a
+ *   request outside is skipped as a whole).  Other slots are not touched.  Plain vector stores, no atomics.
+ * lmod_request_uniform: u[s] = (w >> 8) * 2^-24 in [0, 1) (24 bits: exact in fp32, never 1), w = word 0 of Philox4x32-10 with counter
+ *   (req_id[s], n_gen[s], 0, 0) and key = seed (low word, high word) - the generator of lmod_moe_gate's noise.  A pure function of
+ *   (seed, request, token index): independent of the slot, of the requests beside it and of when it was admitted. */
+int lmod_kv_admit_rows(void* const* dst, const void* const* src, int ntensor, const int* dst_row, const int* lens, int R, int B,
+                       int smax_dst, int smax_src, int width, int max_len, hipStream_t stream);
+int lmod_slot_admit(const int* dst_row, const int* prompt_ids, int ld_prompt, const int* n_prompt_new, const int* lens_new,
+                    const int* req_new, int R, int B, int* hist, int ld_hist, int* n_prompt, int* n_hist, int* n_gen, int* done,
+                    int* cache_lens, int* req_id, hipStream_t stream);
+int lmod_request_uniform(unsigned long long seed, const int* req_id, const int* n_gen, float* u, int B, hipStream_t stream);
+
 /* ---- sparse MoE (DeepSpeed 0.9.5 TopKGate/top1gating/top2gating/MOELayer semantics) ------------
  * logits[T,E] = x.float() @ wg^T  (TopKGate.forward; wg kept fp32).
  * Experts per layer: 1 <= E <= 32 (`--num_experts`, config/args.py:46); the per-token kernels are instantiated for

@@ -10,6 +10,7 @@
 //   combine_fwd/bwd, dispatch_bwd(+router dx), router_wgrad
 // Dispatch itself is lmod_gather_rows with slot_token as the index (empty slots -> zero rows).
 #include "common.h"
+#include "philox.h"
 
 // Experts per layer: the per-token kernels keep one value per expert in registers, so they are compiled for ME = 8 / 16 / 32
 // slots and dispatched on E (`ME_DISPATCH`): E <= 8 — the reference shells' 4 and config 5's 8 — runs exactly the code it
@@ -73,19 +74,10 @@ __global__ __launch_bounds__(256) void router_fwd_kernel(const bf16_t* __restric
     }
 }
 
-// ---------------------------------------------------------------- counter-based random numbers (Philox4x32-10)
+// ---------------------------------------------------------------- counter-based random numbers (Philox4x32-10, philox.h)
 // One call = 4 x 32 random bits for (key = seed, counter = (token + offset, stream)): no state, any token can be drawn by any
 // thread, reproducible from (seed, offset).  Replaces the torch.rand / log launches in front of every MoE layer
 // (sharded_moe.gumbel_rsample draws the top-2 noise; exp_selection_uniform_map the top-1 random-token-selection noise).
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
 // u in (0, 1): 24 random bits + half a step.  mode 1: Gumbel(0,1) = -log(-log(u)); mode 2: the uniform itself.
 template <int ME>
 __device__ __forceinline__ void draw_noise(float (&nz)[ME], long long t, int E, unsigned long long seed,

@@ -60,6 +60,9 @@ SIGNATURES = {
     "lmod_sample_bf16": "pqi" + "pi" + "fif" + "i" + "pq" + "pp" + "p",
     "lmod_logits_process_bf16": "pqii" + "pipp" + "fi" + "ppi" + "ii" + "p",
     "lmod_gen_push_stop": "pp" + "pipp" + "p" + "ii" + "ppi" + "i" + "p",
+    "lmod_kv_admit_rows": "pp" + "i" + "pp" + "iiiiii" + "p",
+    "lmod_slot_admit": "p" + "pippp" + "ii" + "pipppppp" + "p",
+    "lmod_request_uniform": "Q" + "ppp" + "i" + "p",
     "lmod_moe_router_fwd": "ppp" + "iii" + "p",
     "lmod_moe_gate": "pp" + "iiii" + "pppppppppppppp" + "iQQp" + "p",
     "lmod_moe_combine_fwd": "pppppp" + "ii" + "p",

@@ -389,3 +389,134 @@ def gen_push_stop(tokens, done, hist, n_hist, n_prompt, n_gen, eos, pad, stops):
         tail = hist.gather(1, idx).long()
         fin |= fits & (tail == torch.tensor(s, device=tokens.device)[None, :]).all(1)
     return tokens, fin.to(done.dtype), hist, n_hist, n_gen
+
+
+# ---------------------------------------------------------------------------------------------- continuous batching
+class BatchOutput:
+    """`generate_batch(return_dict_in_generate=True)`: sequences (a list, in request order, of 1-D int64 tensors: each request's new
+    tokens, cut after its EOS / stop sequence, no padding), token_logprobs (when sampling: a list of fp32 tensors of the same lengths,
+    the log-probability of each drawn token under the warped distribution; None otherwise) and the scheduler's counters:
+    num_decode_steps, num_decode_forwards, num_admissions, num_prefills, live_row_steps, total_row_steps, live_fraction."""
+
+    def __init__(self, sequences, token_logprobs, scheduler):
+        self.sequences, self.token_logprobs = sequences, token_logprobs
+        for k in ("num_decode_steps", "num_decode_forwards", "num_admissions", "num_prefills", "live_row_steps", "total_row_steps",
+                  "live_fraction"):
+            setattr(self, k, getattr(scheduler, k))
+
+
+def static_batch_steps(max_new_tokens, max_batch_size):
+    """Steps that `generate()` over consecutive static batches of max_batch_size requests runs when every request emits its whole
+    budget: a batch runs until its longest row ends."""
+    m, B = list(max_new_tokens), int(max_batch_size)
+    return sum(max(m[i:i + B]) for i in range(0, len(m), B))
+
+
+class SlotScheduler:
+    """Which request sits in which slot of `generate_batch`, in plain Python (no torch, no device).  A STEP selects one token for
+    every slot (live or not: the batch always runs at max_batch_size rows) and is followed by one decode forward unless no slot is
+    live afterwards.  Policy: before every step all free slots are filled from the queue in request order.
+
+        sched = SlotScheduler(max_new_tokens, max_batch_size)
+        while not sched.finished:
+            for request, slot in sched.admit(): ...          # prefill `request` into `slot`
+            ended = sched.step(stopped)                      # `stopped`: slots whose row hit EOS / a stop sequence in this step
+            ...                                              # ended: [(request, slot)] freed by this step (stopped or budget reached)
+
+    Counters: num_decode_steps (steps), num_decode_forwards (steps after which a slot was still live), num_admissions (requests
+    admitted), num_prefills (admit() calls that admitted something: one prefill pass each), live_row_steps / total_row_steps
+    (rows that emitted a real token / max_batch_size * steps) and their ratio live_fraction — what the feature exists to raise."""
+
+    def __init__(self, max_new_tokens, max_batch_size):
+        self.budget = [int(m) for m in max_new_tokens]
+        B = max_batch_size
+        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+            raise ValueError(f"max_batch_size must be an int >= 1, got {B!r}")
+        if any(m < 1 for m in self.budget):
+            raise ValueError(f"every request needs max_new_tokens >= 1, got {self.budget}")
+        self.B = B
+        self.slot_request = [None] * B             # slot -> request index (None: free)
+        self.n_gen = [0] * B                       # tokens the slot's request has emitted
+        self.next_request = 0
+        self.num_decode_steps = self.num_decode_forwards = self.num_admissions = self.num_prefills = 0
+        self.live_row_steps = self.total_row_steps = 0
+
+    @property
+    def live(self):
+        """{slot: request} of the occupied slots."""
+        return {s: r for s, r in enumerate(self.slot_request) if r is not None}
+
+    @property
+    def finished(self):
+        return self.next_request >= len(self.budget) and all(r is None for r in self.slot_request)
+
+    @property
+    def live_fraction(self):
+        return self.live_row_steps / self.total_row_steps if self.total_row_steps else 0.0
+
+    def admit(self):
+        """Fill every free slot (ascending) from the queue (request order).  Returns [(request, slot)]."""
+        out = []
+        for s in range(self.B):
+            if self.slot_request[s] is None and self.next_request < len(self.budget):
+                self.slot_request[s], self.n_gen[s] = self.next_request, 0
+                out.append((self.next_request, s))
+                self.next_request += 1
+        self.num_admissions += len(out)
+        self.num_prefills += bool(out)
+        return out
+
+    def step(self, stopped=()):
+        """One step: every occupied slot emits a token; a slot in `stopped` or at its request's budget is freed.  Returns the
+        [(request, slot)] freed."""
+        stopped = set(int(s) for s in stopped)
+        live = self.live
+        if not live:
+            raise RuntimeError("step() without a live slot: call admit() first")
+        if not stopped <= set(live):
+            raise ValueError(f"slots {sorted(stopped - set(live))} reported as stopped hold no request")
+        self.num_decode_steps += 1
+        self.total_row_steps += self.B
+        self.live_row_steps += len(live)
+        ended = []
+        for s, r in live.items():
+            self.n_gen[s] += 1
+            if s in stopped or self.n_gen[s] >= self.budget[r]:
+                ended.append((r, s))
+                self.slot_request[s] = None
+        self.num_decode_forwards += any(r is not None for r in self.slot_request)
+        return ended
+
+
+def check_batch_args(requests, max_batch_size=8, max_new_tokens=16, num_beams=1, assistant_model=None, num_return_sequences=1,
+                     past_key_values=None):
+    """The arguments of `generate_batch` that `generate()` does not have, and the modes it leaves out.  Returns each request's
+    max_new_tokens (a list).  ValueError: num_beams > 1, assistant_model, num_return_sequences > 1, past_key_values (out of scope
+    of continuous batching), a bad max_batch_size, a request without `input_ids` or with a budget < 1."""
+    if num_beams != 1:
+        raise ValueError("generate_batch does not support num_beams > 1: beam search needs its beams in adjacent rows")
+    if assistant_model is not None:
+        raise ValueError("generate_batch does not support assistant_model")
+    if num_return_sequences != 1:
+        raise ValueError("generate_batch returns one sequence per request: num_return_sequences > 1 is not supported "
+                         "(list the request more than once)")
+    if past_key_values is not None:
+        raise ValueError("generate_batch does not support past_key_values: it owns its slot cache")
+    B = max_batch_size
+    if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+        raise ValueError(f"max_batch_size must be an int >= 1, got {B!r}")
+    budgets = []
+    for i, rq in enumerate(requests):
+        if not isinstance(rq, dict) or rq.get("input_ids") is None:
+            raise ValueError(f"request {i}: a dict with `input_ids` [S] is expected")
+        unknown = set(rq) - {"input_ids", "images", "max_new_tokens"}
+        if unknown:
+            raise ValueError(f"request {i}: unknown keys {sorted(unknown)} (sampling and stop arguments are per call, not per request)")
+        ids = rq["input_ids"]
+        if getattr(ids, "dim", lambda: 0)() != 1 or ids.numel() < 1:
+            raise ValueError(f"request {i}: input_ids must be a 1-D tensor of at least one token")
+        m = rq.get("max_new_tokens", max_new_tokens)
+        if isinstance(m, bool) or not isinstance(m, int) or m < 1:
+            raise ValueError(f"request {i}: max_new_tokens must be an int >= 1, got {m!r}")
+        budgets.append(m)
+    return budgets

@@ -574,6 +574,62 @@ def gen_push_stop_(tokens, done, hist, n_hist, n_prompt, n_gen, eos, pad, stop=N
          -1 if eos is None else int(eos), 0 if pad is None else int(pad), ptr(sf), ptr(so), ns, R)
 
 
+# ------------------------------------------------------------------------------------------ continuous batching
+def _distinct_slots(dst_row, B):
+    """dst_row: a host list of slot numbers — the kernels trust it, so it is checked here."""
+    rows = [int(r) for r in dst_row]
+    if any(not 0 <= r < B for r in rows) or len(set(rows)) != len(rows):
+        raise ValueError(f"slots must be pairwise distinct and in [0, {B}), got {rows}")
+    return rows
+
+
+def kv_admit_rows(dst, src, dst_row, lens, max_len, tables=None):
+    """dst[t][dst_row[r], :lens[r]] = src[t][r, :lens[r]] for every tensor pair (lists of contiguous bf16 caches, dst [B, smax_dst,
+    width], src [R, smax_src, width]), one launch; everything else in dst stays as it is.  dst_row: a host list of R distinct slots
+    in [0, B) (checked here, trusted by the device); lens [R] device int32; max_len: host upper bound of lens — beyond either smax
+    this raises (LMOD_EINVAL) instead of clamping.  tables: (ptr_table(dst), ptr_table(src)) when the caller keeps them."""
+    assert len(dst) == len(src) and len(dst) > 0
+    d0, s0 = dst[0], src[0]
+    for d, s in zip(dst, src):
+        assert d.dtype == BF16 and s.dtype == BF16 and d.is_contiguous() and s.is_contiguous()
+        assert d.shape == d0.shape and s.shape == s0.shape and s.dim() == 3 and d.dim() == 3 and s.shape[2] == d.shape[2]
+    R, B = s0.shape[0], d0.shape[0]
+    rows = _distinct_slots(dst_row, B)
+    assert len(rows) == R and lens.dtype == torch.int32 and lens.numel() == R
+    if R == 0:
+        return
+    dt, st = tables if tables is not None else (ptr_table(dst), ptr_table(src))
+    call("lmod_kv_admit_rows", ptr(dt), ptr(st), len(dst), ptr(torch.tensor(rows, dtype=torch.int32).to(d0.device)),
+         ptr(lens.contiguous()), R, B, d0.shape[1], s0.shape[1], d0.shape[2], int(max_len))
+
+
+def slot_admit_(dst_row, prompt_ids, n_prompt_new, lens_new, req_new, hist, n_prompt, n_hist, n_gen, done, cache_lens, req_id):
+    """Re-arm the generation state of the slots dst_row (a host list of R distinct slots in [0, B)), in place, one launch
+    (lmod_slot_admit): hist[s, :n] = prompt_ids[r, :n] with n = n_prompt_new[r], n_prompt[s] = n_hist[s] = n, n_gen[s] = done[s] = 0,
+    cache_lens[s] = lens_new[r], req_id[s] = req_new[r].  Everything int32 on the device; prompt_ids [R, >= max n]."""
+    B, R = hist.shape[0], prompt_ids.shape[0]
+    rows = _distinct_slots(dst_row, B)
+    for t in (prompt_ids, n_prompt_new, lens_new, req_new, hist, n_prompt, n_hist, n_gen, done, cache_lens, req_id):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert len(rows) == R and all(t.numel() == R for t in (n_prompt_new, lens_new, req_new))
+    assert all(t.numel() == B for t in (n_prompt, n_hist, n_gen, done, cache_lens, req_id))
+    call("lmod_slot_admit", ptr(torch.tensor(rows, dtype=torch.int32).to(hist.device)), ptr(prompt_ids), prompt_ids.shape[1],
+         ptr(n_prompt_new), ptr(lens_new), ptr(req_new), R, B, ptr(hist), hist.shape[1], ptr(n_prompt), ptr(n_hist), ptr(n_gen),
+         ptr(done), ptr(cache_lens), ptr(req_id))
+
+
+def request_uniform(seed, req_id, n_gen, out=None):
+    """u [B] fp32 in [0, 1): Philox4x32-10 at counter (req_id[s], n_gen[s], 0, 0) under the 64-bit key `seed` — one uniform per
+    slot that depends on the request and its token index only (lmod_request_uniform)."""
+    B = req_id.numel()
+    for t in (req_id, n_gen):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == B
+    u = torch.empty(B, device=req_id.device, dtype=torch.float32) if out is None else out
+    assert u.dtype == torch.float32 and u.is_contiguous() and u.numel() == B
+    call("lmod_request_uniform", int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(req_id), ptr(n_gen), ptr(u), B)
+    return u
+
+
 # ------------------------------------------------------------------------------------------ MoE
 def moe_router_fwd(x, wg):
     T, H = x.shape

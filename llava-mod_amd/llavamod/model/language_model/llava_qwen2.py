@@ -528,6 +528,159 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
             return SampleOutput(seq, torch.stack(lps, 1) if lps else None, cache)
         return GreedyOutput(seq, cache) if return_dict_in_generate else seq
 
+    # ---- continuous batching -------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def generate_batch(self, requests, max_batch_size=8, max_new_tokens=16, eos_token_id=None, pad_token_id=None, do_sample=False,
+                       temperature=1.0, top_k=None, top_p=None, seed=None, num_beams=1, num_return_sequences=1,
+                       return_dict_in_generate=False, past_key_values=None, assistant_model=None, repetition_penalty=1.0,
+                       no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0, stop_sequences=None,
+                       stopping_criteria=None):
+        """Greedy / sampling generation over a LIST of requests with continuous batching: `max_batch_size` slots decode together and
+        a slot whose request has ended (EOS, a stop sequence, its max_new_tokens) is refilled with the next request's freshly
+        prefilled prompt before the next step, while the other slots keep decoding — `generate()` over a batch runs every row until
+        its longest one ends and cannot take a new prompt in.
+
+        requests: a list of dicts — `input_ids` [S_i] (1-D), optional `images` ([n, 3, H, W] or [3, H, W]: the request's own images),
+        optional `max_new_tokens` (default: the call's).  The greedy and sampling arguments of `generate()` apply to the whole call,
+        with the same checks and semantics (eos_token_id, pad_token_id, do_sample / temperature / top_k / top_p / seed,
+        stop_sequences / stopping_criteria, repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens,
+        min_new_tokens); num_beams > 1, assistant_model, num_return_sequences > 1 and past_key_values raise ValueError.  Returns a
+        list, in request order, of 1-D int64 tensors: each request's new tokens, cut after its EOS / stop sequence, no padding; with
+        return_dict_in_generate a `BatchOutput` (sequences, token_logprobs when sampling, the scheduler's counters).
+
+        Allocated once: one slot KVCache of max_batch_size rows, the token history / counters / done flags of
+        `_processed_generate`, a request id per slot and a [max_batch_size, V] logits buffer; the cache is sized for the largest
+        prompt-plus-budget of the list (it grows only if a prefill splices a prompt longer than predicted).  Per step
+        (generation.SlotScheduler decides who sits where; all free slots are filled, in request order, before every step):
+          admit  `_start` on the admitted prompts alone (their own batch size, right-padded) into a temporary cache, one
+                 lmod_kv_admit_rows (every layer's K and V into the slots' rows), one lmod_slot_admit (history, counters, done,
+                 cache length, request id), an indexed copy of the prefill's last-position logits into the slots' logits rows;
+          step   over all max_batch_size rows: lmod_logits_process_bf16 (when a processor is active), the selection
+                 (lmod_row_argmax_bf16, or lmod_request_uniform + lmod_sample_bf16), lmod_gen_push_stop, one read-back (tokens,
+                 done flags, log-probabilities), then one `_decode_step` unless no slot is live.
+        The decode step always runs at M = max_batch_size, so a request's arithmetic does not depend on how many slots are live.
+        A slot without a request stays done: it emits pad, and its cache length is held where it is (a done row rewrites one dead
+        position, so the cache never runs out however long the call lasts).  A request that reaches its own max_new_tokens is
+        stopped by the host (`done.copy_`, as the assisted loop does).  Sampling: the uniform of a request's k-th token is
+        Philox(seed; request index, k) — the same draw whatever slot the request sits in, whichever requests run beside it and
+        whenever it was admitted (`seed` None: drawn from torch's global generator, as generate() does).  The admission prefill is
+        not overlapped with decoding: the running slots wait for it.  A MoE model routes the rows of idle slots too (they take expert
+        capacity in a decode step, as the finished rows of a generate() batch do)."""
+        from ...constants import IMAGE_TOKEN_INDEX
+        from ...generation import BatchOutput, SlotScheduler, check_batch_args, check_logits_args, check_sample_args
+        budgets = check_batch_args(requests, max_batch_size, max_new_tokens, num_beams, assistant_model, num_return_sequences,
+                                   past_key_values)
+        check_sample_args(do_sample, temperature, top_k, top_p, 1)
+        V = self.lm_head.weight.shape[0]
+        lplan = check_logits_args(repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens,
+                                  stop_sequences, stopping_criteria, eos_token_id, V)
+        sched = SlotScheduler(budgets, max_batch_size)
+        if not requests:
+            return BatchOutput([], [] if do_sample else None, sched) if return_dict_in_generate else []
+        B, dev, cfg = max_batch_size, self.model.embed_tokens.weight.device, self.config
+        tower = self.get_image_tower()
+        extra = tower.num_patches - 1 if tower is not None else 0                     # an image token becomes num_patches rows
+        n_ids = [int(rq["input_ids"].numel()) for rq in requests]
+        spliced = [n + (int((rq["input_ids"] == IMAGE_TOKEN_INDEX).sum()) * extra if rq.get("images") is not None else 0)
+                   for n, rq in zip(n_ids, requests)]
+        i32 = dict(device=dev, dtype=torch.int32)
+        st = SimpleNamespace(
+            cache=KVCache(cfg.num_hidden_layers, B, max(s + m for s, m in zip(spliced, budgets)),
+                          cfg.num_key_value_heads * cfg.head_dim, dev),
+            hist=torch.zeros((B, -(-max(n + m for n, m in zip(n_ids, budgets)) // 4) * 4), **i32),   # rows of whole 16-byte vectors
+            n_prompt=torch.zeros(B, **i32), n_hist=torch.zeros(B, **i32), n_gen=torch.zeros(B, **i32),
+            done=torch.ones(B, **i32), req_id=torch.full((B,), -1, **i32),
+            logits=torch.zeros((B, V), device=dev, dtype=BF16))
+        st.tab = K.ptr_table(st.cache.tensors())
+        bad = K.seq_table(lplan.bad, dev) if lplan is not None else None
+        stop = K.seq_table(lplan.stops, dev) if lplan is not None else None
+        process = lplan is not None and lplan.process
+        pad = eos_token_id if pad_token_id is None else pad_token_id
+        if do_sample:
+            seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())        # as generate()
+            u = torch.empty(B, device=dev, dtype=torch.float32)
+        want_lp = do_sample and return_dict_in_generate
+        out, lps = [[] for _ in requests], [[] for _ in requests]
+        was_training = self.training
+        self.eval()
+        try:
+            while not sched.finished:
+                admitted = sched.admit()
+                for with_images in (False, True):                # text-only and image requests splice differently: one prefill each
+                    group = [(r, s) for r, s in admitted if (requests[r].get("images") is not None) == with_images]
+                    if group:
+                        self._admit(requests, budgets, group, st)
+                if process:
+                    K.logits_process_(st.logits, st.hist, st.n_hist, st.n_gen, lplan.penalty, lplan.ngram, bad, lplan.min_new,
+                                      eos_token_id)
+                if do_sample:
+                    K.request_uniform(seed, st.req_id, st.n_gen, out=u)
+                    nxt = K.sample(st.logits, u, temperature, top_k, top_p, stats=want_lp)
+                    if want_lp:
+                        # log p(token) under the warped distribution, as generate(): x[t] - lse - log(kept fraction)
+                        nxt, stats = nxt
+                        x = st.logits.gather(1, nxt.long()[:, None]).squeeze(1).double() / max(float(temperature), 1e-6)
+                        lp = (x - stats[:, 0].double() - torch.log(stats[:, 1].double())).clamp(max=0.0).float()
+                else:
+                    nxt = K.row_argmax(st.logits)
+                K.gen_push_stop_(nxt, st.done, st.hist, st.n_hist, st.n_prompt, st.n_gen, eos_token_id, pad, stop)
+                blk = torch.stack([nxt, st.done] + ([lp.view(torch.int32)] if want_lp else [])).cpu()       # the step's one read-back
+                live = sched.live
+                for s, r in live.items():
+                    out[r].append(int(blk[0, s]))
+                    if want_lp:
+                        lps[r].append(blk[2, s])
+                stopped = [s for s in live if int(blk[1, s]) != 0]
+                by_budget = [s for _, s in sched.step(stopped) if s not in stopped]
+                if by_budget:                                    # the host's stop reaches the device flag
+                    flags = blk[1].clone()
+                    flags[by_budget] = 1
+                    st.done.copy_(flags)
+                if sched.live:
+                    st.logits.copy_(self._decode_step(nxt, st.cache))
+                    st.cache.lens.sub_(st.done)                  # a done row stays at its position: it rewrites one dead entry
+        finally:
+            self.train(was_training)
+        n_out = [len(o) for o in out]
+        seqs = list(torch.tensor([t for o in out for t in o], dtype=torch.int64).to(dev).split(n_out))
+        if not return_dict_in_generate:
+            return seqs
+        logprobs = None
+        if do_sample:
+            flat = torch.stack([v for o in lps for v in o]) if sum(n_out) else torch.zeros(0, dtype=torch.int32)
+            logprobs = list(flat.view(torch.float32).to(dev).split(n_out))
+        return BatchOutput(seqs, logprobs, sched)
+
+    def _admit(self, requests, budgets, group, st):
+        """Admission of generate_batch: prefill the requests of `group` ([(request, slot)]) together and move them into their slots
+        of the state `st` (the slot cache, the generation state, the logits buffer)."""
+        dev = st.logits.device
+        rs, slots = [r for r, _ in group], [s for _, s in group]
+        ids_list = [requests[r]["input_ids"].reshape(-1).to(torch.int64).cpu() for r in rs]
+        n = [int(t.numel()) for t in ids_list]
+        R, S = len(rs), max(n)
+        ids = torch.zeros((R, S), dtype=torch.int64)
+        for j, t in enumerate(ids_list):
+            ids[j, :n[j]] = t
+        mask = torch.arange(S)[None, :] < torch.tensor(n)[:, None]
+        images = None
+        if requests[rs[0]].get("images") is not None:
+            images = torch.cat([im if im.dim() == 4 else im[None] for im in (requests[r]["images"] for r in rs)])
+        tcache, lg = self._start(ids, mask, images, 0, None)
+        lens_h = tcache.lens.cpu().tolist()
+        need = max(l + budgets[r] for l, r in zip(lens_h, rs))
+        if need > st.cache.smax:                                 # the splice made a prompt longer than predicted
+            st.cache.grow(need)
+            st.tab = K.ptr_table(st.cache.tensors())
+        K.kv_admit_rows(st.cache.tensors(), tcache.tensors(), slots, tcache.lens, max(lens_h),
+                        tables=(st.tab, K.ptr_table(tcache.tensors())))
+        prompt = torch.zeros((R, -(-S // 4) * 4), dtype=torch.int32)
+        prompt[:, :S] = ids.to(torch.int32)
+        meta = torch.tensor([n, rs], dtype=torch.int32).to(dev)
+        K.slot_admit_(slots, prompt.to(dev), meta[0].contiguous(), tcache.lens, meta[1].contiguous(), st.hist, st.n_prompt, st.n_hist,
+                      st.n_gen, st.done, st.cache.lens, st.req_id)
+        st.logits[torch.tensor(slots, device=dev)] = lg
+
     @torch.no_grad()
     def _assisted_generate(self, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, draft, k,
                            return_dict_in_generate, past=None):

@@ -32,6 +32,16 @@ tests/_logits_ref.py on device tensors, through model.logits_glue).  One JSON li
 
     python tools/bench_generate.py --only none --processors > profiles/logits_process_ab.jsonl
     python tools/bench_generate.py --only none --processors --processors-only 1 --device-arm-only --reps 1   # B = 1 device arm (trace)
+
+--batched N serves one list of N requests (one image + text each, planted lengths: max_new_tokens drawn per request, one word to a
+paragraph; random weights never emit an EOS) three ways in one process, arms alternating call by call, best of --reps:
+generate_batch (continuous batching at --max-batch-size slots), generate() over consecutive static batches of that size (each runs
+until its longest row ends: the behaviour before generate_batch) and a B = 1 loop.  It also measures one decode step at
+max_batch_size rows and one prefill per admission size that occurs, and prints the prediction
+num_decode_forwards x step + sum over prefill passes of prefill(size), step and prefill counts from generation.SlotScheduler,
+beside the measured wall time.  One JSON line.
+
+    python tools/bench_generate.py --only none --batched 24 > profiles/batched_generate.jsonl
 """
 import argparse
 import json
@@ -227,6 +237,73 @@ def processor_arms(model, Bs, text_len, reps, n1, n2, device_only=False):
         print(json.dumps(rec), flush=True)
 
 
+def batched_arms(model, n_req, B, text_len, reps, n1, n2, seed=0):
+    """Wall ms of serving one request list: generate_batch / static batches of generate() / a B = 1 loop, and the scheduler's prediction."""
+    import random
+    from llavamod.generation import SlotScheduler, static_batch_steps
+    rng = random.Random(seed)
+    lengths = [rng.choice((1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64)) for _ in range(n_req)]     # one word to a paragraph
+    pr = prompts(n_req, text_len, seed)
+    reqs = [dict(input_ids=pr["input_ids"][i], images=pr["images"][i:i + 1], max_new_tokens=lengths[i]) for i in range(n_req)]
+    cut = lambda i, j: {k: v[i:j] for k, v in pr.items()}
+
+    def run(arm):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if arm == "batched":
+            out = model.generate_batch(reqs, max_batch_size=B, return_dict_in_generate=True)
+            got = [len(x) for x in out.sequences]
+        elif arm == "static":
+            got = []
+            for i in range(0, n_req, B):
+                o = model.generate(**cut(i, i + B), max_new_tokens=max(lengths[i:i + B]))
+                got += [min(o.shape[1], m) for m in lengths[i:i + B]]
+        else:
+            got = [model.generate(**cut(i, i + 1), max_new_tokens=lengths[i]).shape[1] for i in range(n_req)]
+        e1.record()
+        torch.cuda.synchronize()
+        assert got == lengths, (arm, got, lengths)
+        return e0.elapsed_time(e1), (out if arm == "batched" else None)
+
+    arms, t, counters = ("batched", "static", "b1"), {}, None
+    for rep in range(reps + 1):                                    # rep 0 warms every arm
+        for a in arms:
+            ms, out = run(a)
+            if rep:
+                t.setdefault(a, []).append(ms)
+            counters = out or counters
+    # the prediction's two unit costs, measured here: a decode step at B rows, a prefill at every admission size that occurs
+    sched, sizes = SlotScheduler(lengths, B), []
+    while not sched.finished:
+        adm = sched.admit()
+        if adm:
+            sizes.append(len(adm))
+        sched.step()
+    prB = cut(0, B)
+    timed(model, prB, 1, n1), timed(model, prB, 1, n2)
+    step_ms = min((timed(model, prB, 1, n2) - timed(model, prB, 1, n1)) / (n2 - n1) for _ in range(reps))
+    prefill_ms = {}
+    for R in sorted(set(sizes)):
+        timed(model, cut(0, R), 1, 1)
+        prefill_ms[R] = min(timed(model, cut(0, R), 1, 1) for _ in range(reps))          # prefill + one token selection
+    predicted = sched.num_decode_forwards * step_ms + sum(prefill_ms[R] for R in sizes)
+    assert counters.num_decode_steps == sched.num_decode_steps and counters.num_prefills == len(sizes)
+    best = {a: min(v) for a, v in t.items()}
+    print(json.dumps({
+        "metric": "generate_batched_wall_ms", "requests": n_req, "max_batch_size": B, "lengths": lengths,
+        "prompt_positions": text_len - 1 + 576, "new_tokens": sum(lengths),
+        "ms_batched": round(best["batched"], 1), "ms_static": round(best["static"], 1), "ms_b1": round(best["b1"], 1),
+        "ms_all": {a: [round(x, 1) for x in v] for a, v in t.items()},
+        "speedup_vs_static": round(best["static"] / best["batched"], 3), "speedup_vs_b1": round(best["b1"] / best["batched"], 3),
+        "num_decode_steps": sched.num_decode_steps, "num_decode_forwards": sched.num_decode_forwards,
+        "static_steps": static_batch_steps(lengths, B), "b1_steps": sum(lengths),
+        "num_admissions": sched.num_admissions, "num_prefills": sched.num_prefills, "admission_sizes": sizes,
+        "live_fraction": round(sched.live_fraction, 4),
+        "live_fraction_static": round(sum(lengths) / (B * static_batch_steps(lengths, B)), 4),
+        "step_ms": round(step_ms, 3), "prefill_ms": {str(k): round(v, 1) for k, v in prefill_ms.items()},
+        "predicted_ms_batched": round(predicted, 1), "measured_over_predicted": round(best["batched"] / predicted, 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--text-len", type=int, default=125, help="text tokens incl. the image placeholder (+575 -> prompt length)")
@@ -241,6 +318,8 @@ def main():
     ap.add_argument("--assistant", type=int, default=None, help="k: assisted generation (self-draft, student draft) against greedy")
     ap.add_argument("--processors", action="store_true", help="greedy with logits processors: plain / device kernels / torch glue")
     ap.add_argument("--processors-only", default=None, help="comma-separated B of the processor arms (default 1,8)")
+    ap.add_argument("--batched", type=int, default=None, help="N requests: generate_batch against static batches and a B = 1 loop")
+    ap.add_argument("--max-batch-size", type=int, default=8, help="slots of the --batched arms")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate.py measures on the GPU"
     from bench import teacher_cfg
@@ -265,6 +344,8 @@ def main():
         append_arms(model, [int(x) for x in a.append.split(",")], a.text_len, a.reps)
     if a.assistant:
         assisted_arms(model, a.assistant, a.text_len, a.reps)
+    if a.batched:
+        batched_arms(model, a.batched, a.max_batch_size, a.text_len, a.reps, a.n1, a.n2)
     if a.processors:
         processor_arms(model, [int(x) for x in a.processors_only.split(",")] if a.processors_only else [1, 8], a.text_len, a.reps,
                        a.n1, a.n2, a.device_arm_only)
