@@ -317,6 +317,41 @@ int lmod_kv_gather_rows(void* const* dst, const void* const* src, int ntensor, c
 int lmod_sample_bf16(const void* logits, long long ld, int V, const float* u, int R, float temperature, int top_k, float top_p,
                      int chunk, void* ws, long long ws_bytes, int* out_token, float* out_stats, hipStream_t stream);
 
+/* ---- speculative sampling (generate(assistant_model=..., speculative_sampling=True); Leviathan et al. ICML'23, HF's
+ *      _speculative_sampling; csrc/specsample.hip) ---------------------------------------------------------------------------
+ * lmod_spec_sample_bf16: verifies k draft tokens per sample so that the emitted tokens are distributed exactly as plain sampling
+ *   from the target.  p_logits [B*(k+1), ld_p] bf16: the target's verification rows, row b*(k+1)+i; q_logits [B*k, ld_q] bf16: the
+ *   rows the draft drew its tokens from, row b*k+i; V <= min(ld_p, ld_q) live columns; draft [B, k], 1 <= k < T_MAX; u_acc [B, k]
+ *   and u_draw [B] fp32 in [0, 1) (device; lmod_spec_uniform makes them).  temperature, top_k, top_p, chunk: as in lmod_sample_bf16.
+ *   p_i / q_i are the warped distributions of row i on each side: lmod_sample_bf16's kept-set rule, fixed-point weight
+ *   w = round(exp((x - rowmax) / T) * 2^40) (0 outside the kept set) and kept mass M.  Position i is accepted iff
+ *   u_acc[b,i] * q_i(d_i) < p_i(d_i) (a draft token outside the target's kept set, or outside [0, V), is always rejected);
+ *   n_acc[b] = the number of accepted positions before the first rejection, 0 for a sample already done.  n_acc < k: next_token is
+ *   the inverse-CDF draw with u_draw[b], in token-id order, from r(x) = max(0, p_n(x) - q_n(x)), n = n_acc; from p_n when r is zero
+ *   everywhere.  n_acc == k: the bonus draw from p_k, the token lmod_sample_bf16 returns for that row and that u.
+ *   done / eos / pad / lens_target / lens_draft / out [B, k+5] / next_token [B]: exactly lmod_spec_accept's layout and update rules
+ *   with target[b, n_acc] = the drawn token: emitted tokens (pad behind) | n_acc | n_emitted | next_token | done.
+ *   out_stats (nullable) [B*(2k+1)][4] fp32: lmod_sample_bf16's stats record of every row, the B*(k+1) p rows first, then the B*k q
+ *   rows.
+ *   Integer-exact and bit-reproducible: U = floor(u * 2^24); accept iff U * w_q(d) * M_p < 2^24 * w_p(d) * M_q (< 2^122, unsigned
+ *   __int128; no 128-bit division); residual weight r(x) = max(0, w_p(x) * M_q - w_q(x) * M_p) >> 24 (<= 2^74, a row sum <= 2^92,
+ *   target = (U * sum) >> 24): a token with p(x) - q(x) >= 2^-40 never weighs 0.  Per-chunk residual masses are stored as two u64
+ *   by one workgroup each; no 128-bit atomics.
+ *   Launches: lmod_sample_bf16's filter passes over all B*(2k+1) rows (2 / 4 / 5 launches without a filter / with one / with both),
+ *   accept (one workgroup per sample), residual mass (grid chunks x B, rows n_acc[b] only, index read on the device), draw (one
+ *   workgroup per sample): 5 / 7 / 8 launches, no host read-back, no allocation.
+ *   ws (8-byte aligned): ws_bytes >= B*(2k+1) * (64 + 3072 * nh + 16 * C) + B * (32 + 16 * C), C = ceil(V / chunk), nh as in
+ *   lmod_sample_bf16.  B * (2k+1) <= 65535, V >= 2; B == 0 is a no-op.  A row without a finite logit on either side rejects its
+ *   position and draws from p_n (token 0 when p_n has none either); nothing is NaN.
+ * lmod_spec_uniform: u[b * n_pos + i] = (w >> 8) * 2^-24 in [0, 1), w = word 0 of Philox4x32-10 with counter
+ *   (row0 + b, round, i, purpose) and key = seed, b < B, i < n_pos: a pure function of (seed, row, round, position, purpose);
+ *   purpose 0: the draft's own draw, 1: the accept test, 2: the residual / bonus draw. */
+int lmod_spec_sample_bf16(const void* p_logits, long long ld_p, const void* q_logits, long long ld_q, int V, const int* draft,
+                          const float* u_acc, const float* u_draw, int B, int k, float temperature, int top_k, float top_p, int chunk,
+                          void* ws, long long ws_bytes, int* done, int eos, int pad, int* lens_target, int* lens_draft, int* out,
+                          int* next_token, float* out_stats, hipStream_t stream);
+int lmod_spec_uniform(unsigned long long seed, int row0, int round, int purpose, int n_pos, float* u, int B, hipStream_t stream);
+
 /* ---- logits processors and stop sequences (generate(repetition_penalty / no_repeat_ngram_size / bad_words_ids / suppress_tokens /
  *      min_new_tokens / stop_sequences); HF GenerationMixin semantics, transformers 5.x) ----------------------------------------
  * Shared state, all int32 and caller-owned: hist [R, ld_hist] (a row's live prompt ids followed by what it has generated),

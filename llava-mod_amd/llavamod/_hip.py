@@ -58,6 +58,8 @@ SIGNATURES = {
     "lmod_beam_topk_bf16": "pqi" + "p" + "iii" + "pq" + "ppp" + "p",
     "lmod_kv_gather_rows": "pp" + "i" + "pp" + "iiiii" + "p",
     "lmod_sample_bf16": "pqi" + "pi" + "fif" + "i" + "pq" + "pp" + "p",
+    "lmod_spec_sample_bf16": "pqpqi" + "ppp" + "ii" + "fif" + "i" + "pq" + "pii" + "pp" + "pp" + "p" + "p",
+    "lmod_spec_uniform": "Q" + "iiii" + "pi" + "p",
     "lmod_logits_process_bf16": "pqii" + "pipp" + "fi" + "ppi" + "ii" + "p",
     "lmod_gen_push_stop": "pp" + "pipp" + "p" + "ii" + "ppi" + "i" + "p",
     "lmod_kv_admit_rows": "pp" + "i" + "pp" + "iiiiii" + "p",

@@ -211,14 +211,20 @@ def spec_accept(draft, target, done, eos, pad, lens_target, lens_draft):
     calls the kernel; this is the statement the tests hold both against).  draft [B, k], target [B, k+1], done [B] (bool / int), lens
     [B]; eos None: no stop token.  Returns (block [B, k+5] = emitted tokens (pad behind) | n_acc | n_emitted | next_token | done,
     next_token [B], done [B], lens_target [B], lens_draft [B]) without modifying its inputs."""
+    k = draft.shape[1]
+    match = (draft == target[:, :k]).long()
+    n_acc = match.cumprod(1).sum(1)
+    n_acc = torch.where(done.bool(), torch.zeros_like(n_acc), n_acc)
+    return _assisted_block(draft, n_acc, target.gather(1, n_acc[:, None])[:, 0], done, eos, pad, lens_target, lens_draft)
+
+
+def _assisted_block(draft, n_acc, corrected, done, eos, pad, lens_target, lens_draft):
+    """The block of one assisted round from n_acc [B] (0 on done rows) and the token behind the accepted drafts, corrected [B]."""
     B, k = draft.shape
     done = done.bool()
     padv = 0 if pad is None else int(pad)
-    match = (draft == target[:, :k]).long()
-    n_acc = match.cumprod(1).sum(1)
-    n_acc = torch.where(done, torch.zeros_like(n_acc), n_acc)
     idx = torch.arange(k + 1, device=draft.device)[None, :]
-    corrected = target.gather(1, n_acc[:, None])
+    corrected = corrected.to(draft.dtype)[:, None]
     tokens = torch.where(idx < n_acc[:, None], torch.cat([draft, draft[:, -1:]], 1), corrected.expand(B, k + 1))
     n_emit = torch.where(done, torch.zeros_like(n_acc), n_acc + 1)
     fin = done.clone()
@@ -231,6 +237,56 @@ def spec_accept(draft, target, done, eos, pad, lens_target, lens_draft):
     nxt = torch.where(fin, torch.full_like(n_acc, padv), corrected[:, 0].long())
     block = torch.cat([tokens.long(), n_acc[:, None], n_emit[:, None], nxt[:, None], fin.long()[:, None]], 1)
     return (block, nxt, fin, lens_target.long() - k + n_acc, lens_draft.long() - k + torch.clamp(n_acc + 1, max=k))
+
+
+def check_spec_sample_args(num_beams, num_assistant_tokens, t_max, num_return_sequences=1, temperature=1.0, top_k=None, top_p=None,
+                           do_sample=False, **unsupported):
+    """Arguments of `generate(assistant_model=..., speculative_sampling=True)`: one sequence per prompt, no beams, k in 1..t_max-1, the
+    temperature / top_k / top_p rules of `check_sample_args`.  `unsupported`: the logits-processor and stop-sequence arguments as
+    name=value; any that is not at its default raises ValueError (out of scope of this mode).  do_sample stays False: combined with
+    assistant_model it keeps raising the greedy-only error of `check_assisted_args`."""
+    defaults = {"repetition_penalty": 1.0, "no_repeat_ngram_size": 0, "min_new_tokens": 0}
+    used = [n for n, v in unsupported.items() if v is not None and v != defaults.get(n)]
+    if used:
+        raise ValueError(f"{', '.join(used)}: logits processors and stop sequences are out of scope of speculative_sampling=True")
+    if do_sample:
+        raise ValueError("assistant_model supports greedy decoding only with do_sample=True: pass speculative_sampling=True and leave "
+                         "do_sample False to sample with an assistant")
+    if num_beams != 1:
+        raise ValueError("speculative_sampling cannot be combined with num_beams > 1")
+    if num_return_sequences != 1:
+        raise ValueError("speculative sampling returns one sequence per prompt: num_return_sequences must be 1")
+    k = num_assistant_tokens
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= t_max - 1:
+        raise ValueError(f"num_assistant_tokens must be an int in 1..{t_max - 1}, got {k!r}")
+    check_sample_args(True, temperature, top_k, top_p, 1)
+
+
+def spec_sample_rule(p, q, draft, u_acc, u_draw, done, eos, pad, lens_target, lens_draft):
+    """The speculative-sampling rule (Leviathan et al.; HF `_speculative_sampling`) in plain torch — what lmod_spec_sample_bf16 computes
+    on the device from logits (the product path calls the kernel; this is the statement the tests hold it against).  p [B, k+1, V] and
+    q [B, k, V]: the WARPED distributions of the target's and the draft's rows (any float dtype; rows sum to 1); draft [B, k];
+    u_acc [B, k], u_draw [B] in [0, 1).  Position i is accepted iff u_acc * q_i(d_i) < p_i(d_i); n_acc = accepted positions before the
+    first rejection (0 on a done row).  The next token is the inverse-CDF draw with u_draw in token-id order (the first token whose
+    cumulative mass exceeds u_draw * total) from max(0, p_n - q_n), n = n_acc < k (from p_n when that is zero everywhere), or from
+    p_k.  Returns spec_accept's tuple (block [B, k+5], next_token, done, lens_target, lens_draft) without modifying its inputs."""
+    B, k = draft.shape
+    V = p.shape[-1]
+    d = draft.long().clamp(0, V - 1)[:, :, None]
+    inside = (draft >= 0) & (draft < V)
+    pd, qd = p[:, :k].gather(2, d)[:, :, 0], q.gather(2, d)[:, :, 0]
+    ok = inside & (u_acc.to(p.dtype) * qd < pd)
+    n_acc = ok.long().cumprod(1).sum(1)
+    n_acc = torch.where(done.bool(), torch.zeros_like(n_acc), n_acc)
+    pn = p.gather(1, n_acc[:, None, None].expand(B, 1, V))[:, 0]
+    qn = torch.cat([q, torch.zeros_like(q[:, :1])], 1).gather(1, n_acc[:, None, None].expand(B, 1, V))[:, 0]
+    r = (pn - qn).clamp_min(0)
+    r = torch.where((r.sum(-1, keepdim=True) > 0) & (n_acc < k)[:, None], r, pn)
+    cdf = r.cumsum(-1)
+    tok = torch.searchsorted(cdf, (u_draw.to(p.dtype) * cdf[:, -1])[:, None].contiguous(), right=True)[:, 0]
+    pos = torch.where(r > 0, torch.arange(V, device=p.device)[None, :], torch.full_like(r, -1, dtype=torch.long)).max(-1).values
+    tok = torch.minimum(tok, pos.clamp_min(0))                                # rounding ran past the end: the last token with mass
+    return _assisted_block(draft.long(), n_acc, tok, done, eos, pad, lens_target, lens_draft)
 
 
 class AssistedBookkeeper:

@@ -524,6 +524,58 @@ def sample(logits, u, temperature=1.0, top_k=None, top_p=None, stats=False):
     return (tokens, st) if stats else tokens
 
 
+# ------------------------------------------------------------------------------------------ speculative sampling
+def spec_sample(p_logits, q_logits, draft, u_acc, u_draw, done, eos, pad, lens_target, lens_draft, temperature=1.0, top_k=None,
+                top_p=None, stats=False):
+    """Speculative sampling's verification on the device (lmod_spec_sample_bf16 in include/lmod_hip.h).  p_logits [B*(k+1), V] (the
+    target's rows, row b*(k+1)+i) and q_logits [B*k, V] (the draft's, row b*k+i): bf16 with the same V live columns (row strides may
+    exceed V); draft [B, k] int32; u_acc [B, k], u_draw [B] fp32 in [0, 1); done [B] and the two caches' lens [B]: int32, updated in
+    place.  Accepts position i iff u_acc * q_i(d_i) < p_i(d_i) on the temperature / top-k / top-p warped distributions, draws the
+    next token from the residual (or from p_k when every draft was accepted).  Returns (block [B, k+5] int32: emitted tokens | n_acc |
+    n_emitted | next_token | done, next_token [B] int32); stats=True adds fp32 [B*(2k+1), 4], `sample`'s record of every row (p rows,
+    then q rows)."""
+    B, k = draft.shape
+    for t in (draft, done, lens_target, lens_draft):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    for t in (u_acc, u_draw):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
+    for t in (p_logits, q_logits):
+        assert t.dtype == BF16 and t.is_cuda and t.dim() == 2 and t.stride(1) == 1
+    V = p_logits.shape[1]
+    assert q_logits.shape[1] == V and p_logits.shape[0] == B * (k + 1) and q_logits.shape[0] == B * k
+    assert u_acc.numel() == B * k and u_draw.numel() == B and done.numel() == B and lens_target.numel() == B and lens_draft.numel() == B
+    R = B * (2 * k + 1)
+    kk = 0 if top_k is None else max(0, min(int(top_k), 2 ** 31 - 1))
+    p = 1.0 if top_p is None else float(top_p)
+    out = torch.empty((B, k + 5), device=draft.device, dtype=torch.int32)
+    nxt = torch.empty(B, device=draft.device, dtype=torch.int32)
+    st = torch.empty((R, 4), device=draft.device, dtype=torch.float32) if stats else None
+    if B == 0:
+        return (out, nxt, st) if stats else (out, nxt)
+    # chunks as `sample` cuts them for R rows
+    c_target = max(1, min(-(-384 // R), -(-V // 512)))
+    chunk = (-(-V // c_target) + 7) // 8 * 8
+    C = -(-V // chunk)
+    nf = int(0 < kk < V) + int(p < 1.0)
+    ws = torch.empty(R * (64 + 3072 * (nf + 1 if nf else 0) + 16 * C) + B * (32 + 16 * C), device=draft.device, dtype=torch.uint8)
+    call("lmod_spec_sample_bf16", ptr(p_logits), p_logits.stride(0), ptr(q_logits), q_logits.stride(0), V, ptr(draft), ptr(u_acc),
+         ptr(u_draw), B, k, float(temperature), kk, p, chunk, ptr(ws), ws.numel(), ptr(done), -1 if eos is None else int(eos),
+         0 if pad is None else int(pad), ptr(lens_target), ptr(lens_draft), ptr(out), ptr(nxt), ptr(st))
+    return (out, nxt, st) if stats else (out, nxt)
+
+
+SPEC_DRAFT, SPEC_ACCEPT, SPEC_DRAW = 0, 1, 2          # lmod_spec_uniform's purposes
+
+
+def spec_uniform(seed, B, round, purpose, n_pos=1, row0=0, device="cuda", out=None):
+    """u [B, n_pos] fp32 in [0, 1): Philox4x32-10 at counter (row0 + b, round, i, purpose) under the 64-bit key `seed` — the uniforms of
+    the speculative loop as a pure function of their coordinates (lmod_spec_uniform)."""
+    u = torch.empty((B, n_pos), device=device, dtype=torch.float32) if out is None else out
+    assert u.dtype == torch.float32 and u.is_cuda and u.is_contiguous() and u.numel() == B * n_pos
+    call("lmod_spec_uniform", int(seed) & 0xFFFFFFFFFFFFFFFF, int(row0), int(round), int(purpose), int(n_pos), ptr(u), B)
+    return u
+
+
 # ------------------------------------------------------------------------------------------ logits processors / stop sequences
 LOGITS_MAX_SEQS = 16          # sequences in the bad-word table, and in the stop table
 LOGITS_MAX_SEQ_LEN = 16       # tokens per sequence

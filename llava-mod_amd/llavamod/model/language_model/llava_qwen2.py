@@ -339,7 +339,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                  num_return_sequences=1, length_penalty=1.0, early_stopping=False, return_dict_in_generate=False,
                  past_key_values=None, assistant_model=None, num_assistant_tokens=5, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0, stop_sequences=None,
-                 stopping_criteria=None, **kwargs):
+                 stopping_criteria=None, speculative_sampling=False, **kwargs):
         """Generation with a KV cache (the reference's eval path calls HF `generate` on the Eval model,
         llava_qwen2_moe.py:629-681; its serving code passes do_sample / temperature / top_p, its eval scripts num_beams).
         Greedy by default; do_sample=True draws from the temperature / top-k / top-p filtered distribution (`seed` makes the
@@ -361,6 +361,12 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         holds accepted tokens behind the returned ones.
 
         assistant_model (with num_assistant_tokens = k in 1..APPEND_T_MAX-1): greedy assisted decoding, `_assisted_generate`.
+        With speculative_sampling=True (and do_sample left False) the assisted loop SAMPLES: `_speculative_generate` draws the drafts
+        from the assistant's temperature / top_k / top_p warped distribution and verifies them with the speculative-sampling rule
+        (lmod_spec_sample_bf16), so the tokens are distributed exactly as generate(do_sample=True) of this model alone; `seed` makes
+        the run reproducible.  One sequence per prompt, no beams, no logits processors or stop sequences, no past_key_values;
+        speculative_sampling=True without assistant_model raises ValueError.  assistant_model with do_sample=True still raises the
+        greedy-only error: folding this mode into do_sample=True is left to a later change that may touch the tests pinning it.
 
         Logits processors and stop sequences (HF names and semantics, transformers 5.x; greedy and sampling only — with
         num_beams > 1 or assistant_model any of them raises ValueError), applied on the device every step by
@@ -383,6 +389,17 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         sequences of at most kernels.LOGITS_MAX_SEQ_LEN tokens per table, ids in [0, V).  A call that uses none of these arguments
         runs the loop below exactly as before."""
         from ...generation import check_logits_args
+        if speculative_sampling:
+            from ...generation import check_spec_sample_args
+            if assistant_model is None:
+                raise ValueError("speculative_sampling=True needs an assistant_model to draft for this model")
+            check_spec_sample_args(num_beams, num_assistant_tokens, K.APPEND_T_MAX, num_return_sequences, temperature, top_k, top_p,
+                                   do_sample, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                   bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens, min_new_tokens=min_new_tokens,
+                                   stop_sequences=stop_sequences, stopping_criteria=stopping_criteria)
+            return self._speculative_generate(input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id,
+                                              assistant_model, num_assistant_tokens, temperature, top_k, top_p, seed,
+                                              return_dict_in_generate, past_key_values)
         lplan = check_logits_args(repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens,
                                   stop_sequences, stopping_criteria, eos_token_id, self.lm_head.weight.shape[0], num_beams,
                                   assistant_model)
@@ -757,6 +774,97 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                 mark()
                 if trace is not None:
                     trace.append(ev)
+        finally:
+            self.train(modes[0]), draft.train(modes[1])
+        seq = book.sequences().to(dev)
+        if return_dict_in_generate:
+            return AssistedOutput(seq, book.num_rounds, 1 + book.num_rounds, book.num_accepted.to(dev), tcache)
+        return seq
+
+    @torch.no_grad()
+    def _speculative_generate(self, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, draft, k,
+                              temperature, top_k, top_p, seed, return_dict_in_generate, past=None):
+        """Speculative sampling, `generate(assistant_model=draft, speculative_sampling=True)`: `_assisted_generate`'s loop with draws
+        in place of arg-maxes.  The first token is a plain lmod_sample_bf16 draw from the target's prefill logits.  Per round: (1) the
+        draft runs its decode steps, each token drawn by lmod_sample_bf16 from the draft's own warped distribution, its logit row
+        copied into a [B*k, ld] buffer; (2) the target runs ONE forward_append over [next_token, d_1 .. d_k]; (3)
+        lmod_spec_sample_bf16 over the B*(k+1) target rows and the B*k draft rows: accept d_i with probability min(1, p_i(d_i) /
+        q_i(d_i)), at the first rejection draw from norm(max(0, p - q)), after k acceptances draw the bonus token from p_k; EOS, done
+        and both caches' lens as lmod_spec_accept; (4) the draft catches up as in the greedy mode, and its last row gives the next
+        round's first draft.  One block read-back per round.  Both sides use min(V_draft, V_target) columns.  Every uniform is
+        lmod_spec_uniform(seed; row, round, position, purpose): draft draws, accept tests and the residual / bonus draw never share
+        one (round 0 is the first token).  `speculative_force_accept` (measurement only): the verification sees the target's rows as
+        the draft's, u_acc = 0 and no top-k / top-p filter, so every draft is accepted (2 filter launches fewer than a filtered
+        call).  Returns the new tokens [B, <= max_new_tokens]; with return_dict_in_generate an `AssistedOutput`."""
+        from ...generation import AssistedBookkeeper, AssistedOutput
+        if past is not None:
+            raise ValueError("assistant_model cannot continue from past_key_values: the draft model has no cache of the earlier turns")
+        modes = (self.training, draft.training)
+        self.eval(), draft.eval()
+        try:
+            tcache, tlogits = self._start(input_ids, attention_mask, images, max_new_tokens + k + 1, None)
+            dcache, _ = draft._start(input_ids, attention_mask, images, max_new_tokens + k + 1, None)
+            B, dev = tlogits.shape[0], tlogits.device
+            V = min(tlogits.shape[1], draft.lm_head.weight.shape[0])
+            seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())   # as generate(do_sample=True)
+            warp = (temperature, top_k, top_p)
+            book = AssistedBookkeeper(B, k, max_new_tokens, eos_token_id, eos_token_id if pad_token_id is None else pad_token_id)
+            nxt = K.sample(tlogits[:, :V], K.spec_uniform(seed, B, 0, K.SPEC_DRAW, device=dev).view(B), *warp)
+            done = book.first(nxt).to(device=dev, dtype=torch.int32).contiguous()
+            lt_h, ld_h = tcache.lens.cpu().long(), dcache.lens.cpu().long()         # host copies of the caches' lens at round start
+            emb_t, emb_d = self.model.embed_tokens.weight, draft.model.embed_tokens.weight
+            ld_q = -(-V // 8) * 8
+            qbuf = torch.empty((B, k, ld_q), device=dev, dtype=BF16)                # the draft's logit rows, row b*k + i
+            u_d = torch.empty((B, k), device=dev, dtype=torch.float32)
+            u_a, u_n = torch.empty_like(u_d), torch.empty(B, device=dev, dtype=torch.float32)
+            force = getattr(self, "speculative_force_accept", False)
+            have_first, rnd = False, 0
+            d_first = None
+            while not book.finished:
+                rnd += 1
+                if int(ld_h.max()) + k + 2 > dcache.smax:
+                    dcache.grow(int(ld_h.max()) + k + 2 + max_new_tokens)
+                if not have_first:
+                    K.spec_uniform(seed, B, rnd, K.SPEC_DRAFT, k, out=u_d)
+                K.spec_uniform(seed, B, rnd, K.SPEC_ACCEPT, k, out=u_a)
+                K.spec_uniform(seed, B, rnd, K.SPEC_DRAW, 1, out=u_n)
+                tok, drafts = (nxt, []) if not have_first else (d_first, [d_first])
+                while len(drafts) < k:
+                    i = len(drafts)
+                    qbuf[:, i, :V].copy_(draft._decode_step(tok, dcache)[:, :V])
+                    tok = K.sample(qbuf[:, i, :V], u_d[:, i].contiguous(), *warp)
+                    drafts.append(tok)
+                draft_t = torch.stack(drafts, 1).contiguous()
+                chunk = torch.cat([nxt[:, None], draft_t], 1).reshape(-1).contiguous()
+                hid = self.model.forward_append(K.gather_rows(emb_t, None, chunk, emb_t.shape[1]), tcache, k + 1, max_len=int(lt_h.max()))
+                plog = ops.linear_fwd(hid, self.head())
+                vwarp = warp
+                if force:                   # measurement only: q := p, u_acc = 0, no filter in the verification: every draft accepted
+                    qbuf[:, :, :V].copy_(plog.view(B, k + 1, -1)[:, :k, :V])
+                    u_a.zero_()
+                    vwarp = (temperature, None, None)
+                block, nxt = K.spec_sample(plog[:, :V], qbuf.view(B * k, ld_q)[:, :V], draft_t, u_a, u_n, done, eos_token_id, book.pad,
+                                           tcache.lens, dcache.lens, *vwarp)
+                blk = block.cpu()                                                   # the round's one read-back
+                book.update(blk)
+                n_acc = blk[:, k + 1].long()
+                if book.finished:
+                    break
+                done.copy_(book.stopped.to(torch.int32))
+                full = n_acc == k
+                idx = torch.tensor([2 * b + j for b in range(B) for j in ((0, 1) if bool(full[b]) else (1,))], dtype=torch.long)
+                toks = torch.stack([draft_t[:, k - 1], nxt], 1).reshape(-1)[idx.to(dev)].contiguous()
+                n_ch = 1 + full.to(torch.int32)
+                hid = draft.model.forward_append(K.gather_rows(emb_d, None, toks, emb_d.shape[1]), dcache, n_ch.to(dev), T=2,
+                                                 max_len=int((ld_h + torch.clamp(n_acc + 1, max=k)).max()))
+                lt_h, ld_h = lt_h + n_acc + 1, ld_h + n_acc + 1
+                last = (n_ch.cumsum(0) - 1).to(torch.int32).to(dev)
+                hl = K.gather_rows(hid, None, last, hid.shape[1])
+                # the next round's first draft: drawn from the catch-up's last row with that round's first draft uniform
+                qbuf[:, 0, :V].copy_(ops.linear_fwd(hl, draft.head())[:, :V])
+                K.spec_uniform(seed, B, rnd + 1, K.SPEC_DRAFT, k, out=u_d)
+                d_first = K.sample(qbuf[:, 0, :V], u_d[:, 0].contiguous(), *warp)
+                have_first = True
         finally:
             self.train(modes[0]), draft.train(modes[1])
         seq = book.sequences().to(dev)

@@ -42,6 +42,12 @@ num_decode_forwards x step + sum over prefill passes of prefill(size), step and 
 beside the measured wall time.  One JSON line.
 
     python tools/bench_generate.py --only none --batched 24 > profiles/batched_generate.jsonl
+
+--speculative k times generate(do_sample=True) against generate(assistant_model=student, speculative_sampling=True) at B in {1, 8}
+(speculative_arms); --spec-kernel-only k runs lmod_spec_sample_bf16 alone at V = 151936 for a kernel trace.
+
+    python tools/bench_generate.py --only none --speculative 5 > profiles/spec_sample_ab.jsonl
+    rocprofv3 --kernel-trace --stats -- python tools/bench_generate.py --spec-kernel-only 5
 """
 import argparse
 import json
@@ -195,6 +201,75 @@ def assisted_arms(model, k, text_len, reps, n_new=33):
     print(json.dumps(rec), flush=True)
 
 
+def speculative_arms(model, k, text_len, reps, Bs=(1, 8), n_new=33, sample=dict(temperature=1.0, top_p=0.9)):
+    """ms per new token of plain generate(do_sample=True) (the baseline: the path before speculative sampling existed) against
+    generate(assistant_model=student, speculative_sampling=True), arms alternating call by call in one process, best of `reps`.
+    Random weights give a meaningless acceptance rate, so two arms bracket it: student_draft (lower bound: the random student's drafts
+    are nearly always rejected) and student_forced (upper bound: model.speculative_force_accept replaces the draft's logit rows by the
+    target's, every draft is accepted; measurement only).  One JSON line per B, with the measured acceptance and rounds."""
+    from bench import moe_model_args, student_cfg
+    from llavamod.model import LLaVAMoDQwen2ForCausalLM
+    student = LLaVAMoDQwen2ForCausalLM(student_cfg(4), device="cuda")
+    student.initialize_moe_modules(moe_model_args(4))
+    student.eval()
+    for B in Bs:
+        pr = prompts(B, text_len)
+
+        def run(arm):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            if arm == "plain":
+                kw = dict(do_sample=True, seed=0, **sample)
+            else:
+                kw = dict(assistant_model=student, speculative_sampling=True, num_assistant_tokens=k, seed=0,
+                          return_dict_in_generate=True, **sample)
+                model.speculative_force_accept = arm == "student_forced"
+            e0.record()
+            out = model.generate(**pr, max_new_tokens=n_new, **kw)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1), out
+
+        arms = ("plain", "student_draft", "student_forced")
+        res, stats = {a: [] for a in arms}, {}
+        for rep in range(reps + 1):                                # rep 0 warms every arm
+            for a in arms:
+                ms, out = run(a)
+                if rep:
+                    res[a].append(ms)
+                if a != "plain":
+                    stats[a] = dict(rounds=out.num_rounds, accepted=int(out.num_accepted.sum()), tokens=int(out.sequences.shape[1]),
+                                    acceptance=round(float(out.num_accepted.sum()) / (B * k * out.num_rounds), 4))
+        del model.speculative_force_accept
+        # the prefill(s) are inside every figure: ms per call / new tokens
+        rec = {"metric": "speculative_sampling_ms_per_new_token", "B": B, "k": k, "new_tokens": n_new, **sample,
+               "prompt_positions": text_len - 1 + 576}
+        for a in arms:
+            rec[f"{a}_ms_per_token"] = round(min(res[a]) / n_new, 3)
+            rec[f"{a}_ms_per_token_all"] = [round(v / n_new, 3) for v in res[a]]
+        rec.update({f"{a}_{n}": v for a, st in stats.items() for n, v in st.items()})
+        print(json.dumps(rec), flush=True)
+
+
+def spec_kernel_only(k, reps=20, V=151936):
+    """lmod_spec_sample_bf16 alone at the vocabulary's size, B in {1, 8} (for a kernel trace): device ms per call by events."""
+    from llavamod import kernels as K
+    for B in (1, 8):
+        g = torch.Generator(device="cuda").manual_seed(B)
+        P = (3 * torch.randn(B * (k + 1), V, device="cuda", generator=g)).to(torch.bfloat16)
+        Q = (P.view(B, k + 1, V)[:, :k].float() + 0.5 * torch.randn(B, k, V, device="cuda", generator=g)).to(torch.bfloat16).view(B * k, V)
+        draft = K.sample(Q, torch.rand(B * k, device="cuda", generator=g), 1.0, None, 0.9).view(B, k).contiguous()
+        ua, un = torch.rand(B, k, device="cuda", generator=g), torch.rand(B, device="cuda", generator=g)
+        i32 = dict(device="cuda", dtype=torch.int32)
+
+        def call(tk, tp):
+            K.spec_sample(P, Q, draft, ua, un, torch.zeros(B, **i32), None, 0, torch.full((B,), 700, **i32), torch.full((B,), 700, **i32),
+                          1.0, tk, tp)
+        for name, (tk, tp) in (("none", (None, None)), ("top_p", (None, 0.9)), ("top_k_top_p", (50, 0.9))):
+            call(tk, tp)
+            print(json.dumps({"metric": "spec_sample_kernel_ms_per_call", "B": B, "k": k, "V": V, "filter": name,
+                              "ms": round(_ms(lambda: call(tk, tp), reps), 4)}), flush=True)
+
+
 PROCESSORS = dict(repetition_penalty=1.1, no_repeat_ngram_size=3, stop_sequences=[[151640, 151641]])
 
 
@@ -320,8 +395,12 @@ def main():
     ap.add_argument("--processors-only", default=None, help="comma-separated B of the processor arms (default 1,8)")
     ap.add_argument("--batched", type=int, default=None, help="N requests: generate_batch against static batches and a B = 1 loop")
     ap.add_argument("--max-batch-size", type=int, default=8, help="slots of the --batched arms")
+    ap.add_argument("--speculative", type=int, default=None, help="k: speculative sampling (student draft / forced) against do_sample")
+    ap.add_argument("--spec-kernel-only", type=int, default=None, help="k: lmod_spec_sample_bf16 alone, no model (for a kernel trace)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate.py measures on the GPU"
+    if a.spec_kernel_only:
+        return spec_kernel_only(a.spec_kernel_only)
     from bench import teacher_cfg
     from llavamod.model import LlavaQwen2ForCausalLM
     model = LlavaQwen2ForCausalLM(teacher_cfg(), device="cuda")
@@ -344,6 +423,8 @@ def main():
         append_arms(model, [int(x) for x in a.append.split(",")], a.text_len, a.reps)
     if a.assistant:
         assisted_arms(model, a.assistant, a.text_len, a.reps)
+    if a.speculative:
+        speculative_arms(model, a.speculative, a.text_len, a.reps)
     if a.batched:
         batched_arms(model, a.batched, a.max_batch_size, a.text_len, a.reps, a.n1, a.n2)
     if a.processors:
