@@ -253,6 +253,21 @@ int lmod_kv_append_rows(const void* qkv, int ldqkv, int kcol, int vcol, int widt
 int lmod_spec_accept(const int* draft, const int* target, int k, int* done, int eos, int pad, int* lens_target, int* lens_draft,
                      int* out, int* next_token, int B, hipStream_t stream);
 
+/* ---- long-chunk cache extension (csrc/attn_extend.hip) ----------------------------------------
+ * lmod_attn_extend: lmod_attn_append's contract without its chunk limit — causal flash attention (MFMA) of a ragged chunk of
+ *   1 <= T <= 65535 new queries per sample against a KV cache that already holds a prefix and the chunk's own keys and values: a later
+ *   turn of a conversation, images included, in one pass.  Caches [B, smax, ld_cache] (kv head hk at column hk*hd), lens[b] = valid
+ *   positions AFTER the append; packed query rows q[cu_new[b] + t], t < n_b, 0 <= n_b <= T (cu_new: device int[B+1]; NULL: every
+ *   sample brings exactly T rows, row b*T + t); output rows are laid out like q.  Query t of sample b sees the keys
+ *   k <= lens[b] - n_b + t; a row without a visible key is exactly 0; a sample with n_b = 0 writes nothing.  Positions >= lens[b] are
+ *   never read (they may hold anything) and no address at or beyond (b + 1) * smax rows is formed.  hd 64 or 128, nh % nkv == 0
+ *   (LMOD_EUNSUPPORTED for another hd, T, B or nh > 65535).  ldq, ldo, ld_cache multiples of 8 and q, out, caches 16-byte aligned
+ *   (LMOD_EINVAL).  Scores and the online softmax in fp32; P enters the P V MFMAs as three bf16 terms that hold the fp32 value
+ *   exactly; one rounding, of O, to bf16.  No key split and no atomics: two calls give the same bits.  Where both apply (T <= 16) it
+ *   computes what lmod_attn_append computes (another summation order: the same kind of bound, not the same bits). */
+int lmod_attn_extend(const void* q, const void* kcache, const void* vcache, const int* lens, const int* cu_new, void* out, int B,
+                     int T, int nh, int nkv, int hd, int smax, int ldq, int ld_cache, int ldo, float scale, hipStream_t stream);
+
 /* ---- multimodal splice / loss-row plans built on the device ----------------------------------------
  * prepare_inputs_labels_for_multimodal (llava_arch.py:155-334) as index maps, from int tensors already on the device.
  * lmod_splice_count: per sample the spliced length (pads stripped by attention_mask, every -200 token replaced by

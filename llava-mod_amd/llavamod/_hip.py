@@ -55,6 +55,7 @@ SIGNATURES = {
     "lmod_attn_append": "pppppp" + "iiiiiiiii" + "f" + "i" + "pq" + "p",
     "lmod_kv_append_rows": "piiii" + "pp" + "pp" + "iiiii" + "p",
     "lmod_spec_accept": "pp" + "i" + "p" + "ii" + "pppp" + "i" + "p",
+    "lmod_attn_extend": "pppppp" + "iiiiiiiii" + "f" + "p",
     "lmod_beam_topk_bf16": "pqi" + "p" + "iii" + "pq" + "ppp" + "p",
     "lmod_kv_gather_rows": "pp" + "i" + "pp" + "iiiii" + "p",
     "lmod_sample_bf16": "pqi" + "pi" + "fif" + "i" + "pq" + "pp" + "p",

@@ -401,6 +401,7 @@ def attn_decode(q, kcache, vcache, lens, nh, nkv, hd, scale):
 
 # ------------------------------------------------------------------------------------------ multi-token cache extension
 APPEND_T_MAX = 16          # csrc/append.hip: tokens per sample in one chunk; (nh / nkv) * T <= 128 as well
+EXTEND_T_MAX = 65535       # csrc/attn_extend.hip: rows per sample in one chunk (a grid dimension)
 _APPEND_WS = {}
 
 
@@ -429,6 +430,21 @@ def attn_append(q, kcache, vcache, lens, nh, nkv, hd, scale, T, cu_new=None, nsp
             _APPEND_WS[key] = ws = torch.empty(need, device=q.device, dtype=torch.uint8)
     call("lmod_attn_append", ptr(q), ptr(kcache), ptr(vcache), ptr(lens), ptr(cu_new), ptr(out), B, T, nh, nkv, hd, kcache.shape[1],
          q.stride(0), kcache.stride(1), out.stride(0), float(scale), ns, ptr(ws), need)
+    return out
+
+
+def attn_extend(q, kcache, vcache, lens, nh, nkv, hd, scale, T, cu_new=None):
+    """attn_append's contract for chunks of any length (1 <= T <= 65535 rows per sample): the MFMA flash kernel of
+    csrc/attn_extend.hip.  q [R, nh*hd] packed rows (views fine, row stride a multiple of 8), sample b owns rows
+    cu_new[b] .. cu_new[b+1]-1 (None: exactly T rows each); lens [B] int32 = valid positions after the append.  -> out [R, nh*hd]."""
+    B = kcache.shape[0]
+    assert q.dtype == BF16 and q.stride(1) == 1 and kcache.dtype == BF16 and vcache.dtype == BF16
+    assert kcache.stride(2) == 1 and vcache.stride() == kcache.stride() and kcache.stride(0) == kcache.shape[1] * kcache.stride(1)
+    assert lens.dtype == torch.int32 and lens.numel() == B and (cu_new is None or (cu_new.dtype == torch.int32 and cu_new.numel() == B + 1))
+    assert cu_new is not None or q.shape[0] == B * T
+    out = torch.empty((q.shape[0], nh * hd), device=q.device, dtype=BF16)
+    call("lmod_attn_extend", ptr(q), ptr(kcache), ptr(vcache), ptr(lens), ptr(cu_new), ptr(out), B, T, nh, nkv, hd, kcache.shape[1],
+         q.stride(0), kcache.stride(1), out.stride(0), float(scale))
     return out
 
 

@@ -237,17 +237,26 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
             cache = past
             dev = cache.lens.device
             if input_ids.shape[1] > 1:           # a chunk of new tokens: fp32 logits [B, T, V], rows of padded positions zero; grows the cache
-                return out_cls(loss=None, logits=self._append_chunk(input_ids, attention_mask, cache, "all"), past_key_values=cache)
+                return out_cls(loss=None, logits=self._append_chunk(input_ids, attention_mask, cache, "all", images=images),
+                               past_key_values=cache)
             if int(cache.lens.max()) >= cache.smax:
                 raise ValueError("KV cache exhausted: raise `generation_budget` before the prefill")
             logits = self._decode_step(input_ids[:, -1].to(device=dev, dtype=torch.int32), cache)
         return out_cls(loss=None, logits=logits.float().unsqueeze(1), past_key_values=cache)
 
+    extend_min_tokens = 17             # a chunk whose longest sample has at least this many live tokens runs in ONE pass
+    #                                    (forward_extend / lmod_attn_extend); shorter ones in pieces of APPEND_T_MAX.  Huge: always pieces
+
     @torch.no_grad()
-    def _append_chunk(self, input_ids, attention_mask, cache, want, reserve=0):
-        """Push input_ids [B, T] (text only; attention_mask None or [B, T], right-padded, covering the chunk only) through the model
-        against `cache` — the continuation of a conversation — in pieces of at most APPEND_T_MAX tokens per sample
-        (Qwen2Model.forward_append; only live rows enter the decoder).  The cache grows if it has to (plus `reserve` positions).
+    def _append_chunk(self, input_ids, attention_mask, cache, want, reserve=0, images=None):
+        """Push input_ids [B, T] (attention_mask None or [B, T], right-padded, covering the chunk only) through the model against
+        `cache` — the continuation of a conversation.  Only live rows enter the decoder.  The cache grows if it has to (plus
+        `reserve` positions).
+        Text-only chunk whose longest sample has fewer than `extend_min_tokens` live tokens: pieces of at most APPEND_T_MAX tokens
+        per sample (Qwen2Model.forward_append).  Otherwise ONE pass over the packed live rows (Qwen2Model.forward_extend).
+        images: the chunk's IMAGE_TOKEN_INDEX placeholders are spliced exactly as `_prefill` splices a prompt (right-padded, `unpad`
+        off, lengths from the splice plan) and the spliced rows go through forward_extend whatever their count; T below is then the
+        longest SPLICED length.  An image token without `images` raises.
         want="all": fp32 logits [B, T, V] with zero rows on padded positions; want="last": bf16 logits [B, V] of every sample's last
         live token."""
         from ...constants import IMAGE_TOKEN_INDEX
@@ -256,8 +265,6 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         B, T = ids.shape
         if B != cache.lens.shape[0]:
             raise ValueError(f"the cache holds {cache.lens.shape[0]} samples, input_ids {B}")
-        if bool((ids == IMAGE_TOKEN_INDEX).any()):
-            raise ValueError("image tokens in a continuation chunk are not supported: a chunk fed with past_key_values is text-only")
         if attention_mask is not None:
             amd = attention_mask.to(device=dev).to(torch.int32)
             if tuple(amd.shape) != (B, T):
@@ -270,6 +277,21 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                 raise ValueError("every sample of a continuation chunk needs at least one live token")
         else:
             n_all = torch.full((B,), T, device=dev, dtype=torch.int32)
+        emb = None
+        if images is not None:
+            unpad, self.unpad = getattr(self, "unpad", False), False       # the KV cache is laid out per padded sample
+            try:
+                _, _, _, _, embeds, _ = self.prepare_inputs_labels_for_multimodal(input_ids, None, attention_mask, None, None, images)
+            finally:
+                self.unpad = unpad
+            if embeds is not None:
+                # spliced chunk: the plan knows every sample's real length; pack the live rows sample-major
+                n_all = torch.from_numpy(self._plan.lens_np.astype("int32")).to(dev)
+                T = embeds.shape[1]
+                emb = embeds[torch.arange(T, device=dev)[None, :] < n_all[:, None]].contiguous()
+        if emb is None and bool((ids == IMAGE_TOKEN_INDEX).any()):
+            raise ValueError("image tokens in a continuation chunk need their `images`: without them a chunk fed with "
+                             "past_key_values is text-only")
         n_host = n_all.cpu()
         hi = int(cache.lens.max())
         if hi + T + reserve > cache.smax:
@@ -277,6 +299,16 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         emb_w = self.model.embed_tokens.weight
         V = self.lm_head.weight.shape[0]
         out = torch.zeros((B, T, V), device=dev, dtype=torch.float32) if want == "all" else torch.empty((B, V), device=dev, dtype=BF16)
+        if emb is not None or int(n_host.max()) >= self.extend_min_tokens:
+            live = torch.arange(T, device=dev)[None, :] < n_all[:, None]
+            if emb is None:
+                emb = K.gather_rows(emb_w, None, ids[live].to(torch.int32).contiguous(), emb_w.shape[1])   # packed, sample-major
+            uniform = emb.shape[0] == B * T
+            hidden = self.model.forward_extend(emb, cache, T if uniform else n_all, T=T, max_len=hi)
+            if want == "all":
+                out[live] = ops.linear_fwd(hidden, self.head()).float()
+                return out
+            return ops.linear_fwd(hidden[(n_host.cumsum(0) - 1).to(dev)].contiguous(), self.head())
         for j0 in range(0, T, K.APPEND_T_MAX):
             Tp = min(K.APPEND_T_MAX, T - j0)
             n_p = (n_all - j0).clamp(0, Tp).to(torch.int32)
@@ -299,17 +331,16 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         return out
 
     def _start(self, input_ids, attention_mask, images, max_new_tokens, past):
-        """Where every generation mode begins: the prompt's prefill, or — continuing from `past` — the new turn's tokens through the chunk
-        path.  Returns (cache with room for max_new_tokens more positions, bf16 logits [B, V] of every sample's last token)."""
+        """Where every generation mode begins: the prompt's prefill, or — continuing from `past` — the new turn's tokens (with the
+        turn's own `images`, if it has any) through the chunk path.  Returns (cache with room for max_new_tokens more positions, bf16
+        logits [B, V] of every sample's last token)."""
         if past is None:
             return self._prefill(input_ids, attention_mask, images, max_new_tokens)
-        if images is not None:
-            raise ValueError("a continuation (past_key_values) is text-only: images belong to the first turn")
-        if input_ids.shape[1] == 1:
+        if input_ids.shape[1] == 1 and images is None:
             if int(past.lens.max()) + 1 + max_new_tokens > past.smax:
                 past.grow(int(past.lens.max()) + 1 + max_new_tokens)
             return past, self._decode_step(input_ids[:, 0].to(device=past.lens.device, dtype=torch.int32), past)
-        return past, self._append_chunk(input_ids, attention_mask, past, "last", reserve=max_new_tokens)
+        return past, self._append_chunk(input_ids, attention_mask, past, "last", reserve=max_new_tokens, images=images)
 
     @torch.no_grad()
     def _decode_step(self, tokens, cache):
@@ -350,8 +381,8 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         sequence's EOS hold pad_token_id); with do_sample and return_dict_in_generate a `SampleOutput` (sequences, token_logprobs).
 
         past_key_values (a KVCache of an earlier generate() / use_cache forward): continue from it — `input_ids` [B, T] (and an
-        optional right-padded attention_mask [B, T]) are the NEW turn only, text-only, and run through the chunk path
-        (`_append_chunk`) instead of a prefill; every mode works from there.  The cache holds each position that was fed: the prompt
+        optional right-padded attention_mask [B, T]) are the NEW turn only and run through the chunk path (`_append_chunk`) instead
+        of a prefill; the turn may bring `images` of its own for its IMAGE_TOKEN_INDEX placeholders; every mode works from there.  The cache holds each position that was fed: the prompt
         and every generated token but each row's last, which a caller chaining turns puts in front of the next turn's tokens.
         With return_dict_in_generate every mode's result carries `past_key_values`.  NOTE, a change of an existing path: greedy
         generate(return_dict_in_generate=True) used to return the bare token tensor and now returns a `GreedyOutput` (sequences,

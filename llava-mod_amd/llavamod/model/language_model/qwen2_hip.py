@@ -164,6 +164,17 @@ class Qwen2Attention(nn.Module):
         o = K.attn_append(qkv[:, :nh * hd], kc, vc, rt.lens_after, nh, nkv, hd, 1.0 / math.sqrt(hd), rt.T, cu_new=rt.cu)
         return ops.linear_fwd(o, self._o.ensure())
 
+    def forward_extend(self, x, rt):
+        """forward_append for a chunk of any length: the same projection, rope_ at lens_before + t and lmod_kv_append_rows, then
+        lmod_attn_extend (MFMA flash attention of the chunk against the cache, P carried at fp32 precision as in forward_append)."""
+        nh, nkv, hd = self.nh, self.nkv, self.hd
+        qkv = ops.linear_fwd(x, self._qkv.ensure())
+        K.rope_(qkv, rt.cos, rt.sin, rt.pos, nh + nkv, hd)
+        kc, vc = rt.cache.k[rt.layer], rt.cache.v[rt.layer]
+        K.kv_append_rows(qkv, nh * hd, (nh + nkv) * hd, nkv * hd, kc, vc, rt.lens_before, rt.T, rt.max_len_after, cu_new=rt.cu)
+        o = K.attn_extend(qkv[:, :nh * hd], kc, vc, rt.lens_after, nh, nkv, hd, 1.0 / math.sqrt(hd), rt.T, cu_new=rt.cu)
+        return ops.linear_fwd(o, self._o.ensure())
+
 
 class Qwen2MLP(nn.Module):
     def __init__(self, cfg, device):
@@ -233,7 +244,7 @@ class Qwen2DecoderLayer(nn.Module):
         """forward_decode over the packed live rows of a chunk: only they enter the layer, so a MoE layer routes exactly the live
         tokens and padded positions take no expert capacity."""
         n1, _, h = K.rmsnorm_fwd(delta, self.input_layernorm.weight, self.input_layernorm.variance_epsilon, res=res)
-        a = self.self_attn.forward_append(n1, rt)
+        a = self.self_attn.forward_extend(n1, rt) if rt.extend else self.self_attn.forward_append(n1, rt)
         n2, _, h2 = K.rmsnorm_fwd(a, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon, res=h)
         m = self.mlp(n2, rt)
         if isinstance(m, tuple):
@@ -307,12 +318,22 @@ class Qwen2Model(nn.Module):
         brings no row and keeps its cache as it is).  Appends to
         `cache` (growing it if the chunk would run past smax) and returns the final-normed hidden states [R, H].  max_len: the
         caller's upper bound of cache.lens when it has one (saves the read-back of lens.max())."""
+        return self._forward_chunk(inputs_embeds, cache, n_new, T, max_len, K.APPEND_T_MAX, False)
+
+    def forward_extend(self, inputs_embeds, cache, n_new, T=None, max_len=None):
+        """forward_append without its 16-token limit: a chunk of up to EXTEND_T_MAX tokens per sample in ONE pass over the weights,
+        its attention by lmod_attn_extend.  Same arguments, same cache growth, same result layout."""
+        return self._forward_chunk(inputs_embeds, cache, n_new, T, max_len, K.EXTEND_T_MAX, True)
+
+    def _forward_chunk(self, inputs_embeds, cache, n_new, T, max_len, t_max, extend):
+        """The bookkeeping forward_append and forward_extend share: chunk positions lens_before + t, the packed rows' cu offsets,
+        cache growth, the layer loop (a layer's attention is forward_extend iff `extend`) and the lens update."""
         dev = inputs_embeds.device
         R, B = inputs_embeds.shape[0], cache.lens.shape[0]
         ragged = torch.is_tensor(n_new)
         T = int(n_new) if not ragged else int(T)
-        if not 1 <= T <= K.APPEND_T_MAX:
-            raise ValueError(f"a chunk holds 1..{K.APPEND_T_MAX} tokens per sample, got {T}")
+        if not 1 <= T <= t_max:
+            raise ValueError(f"a chunk holds 1..{t_max} tokens per sample, got {T}")
         if not ragged and R != B * T:
             raise ValueError(f"{R} rows for {B} samples x {T} tokens")
         hi = (int(cache.lens.max()) if max_len is None else int(max_len)) + T
@@ -333,7 +354,7 @@ class Qwen2Model(nn.Module):
         cos, sin = rope_tables(self.config.head_dim, max(self.config.max_position_embeddings, cache.smax),
                                self.config.rope_theta, dev)
         rt = SimpleNamespace(B=B, S=T, T=T, cos=cos, sin=sin, pos=pos, seqlens=None, cache=cache, layer=0, cu=cu,
-                             lens_before=lens_before, lens_after=lens_after, max_len_after=hi)
+                             lens_before=lens_before, lens_after=lens_after, max_len_after=hi, extend=extend)
         delta, res = inputs_embeds, None
         with torch.no_grad():
             for i, layer in enumerate(self.layers):

@@ -23,6 +23,14 @@ acceptance forced (the round's cost at full acceptance), against plain greedy; e
 accept / catch-up by events inside the loop (model.assisted_trace).
 
     python tools/bench_generate.py --only none --append 2,4,8 > profiles/append_attn.jsonl
+
+--extend T (comma-separated list) times a second turn of T text tokens after one image-plus-text prefill, B in {1, 8}, two arms
+alternating call by call in one process, best of --reps: the extend path (one pass of Qwen2Model.forward_extend, lmod_attn_extend)
+and the piece loop (extend_min_tokens raised: ceil(T / 16) passes of forward_append, the only path before lmod_attn_extend existed).
+Both return the last row's logits (`_append_chunk(..., "last")`).  One JSON line per (B, T).
+
+    python tools/bench_generate.py --only none --extend 32,160,640 > profiles/extend_attention.jsonl
+    rocprofv3 --kernel-trace --stats -- python tools/bench_generate.py --only none --extend 640 --extend-only 1 --extend-arm-only --reps 1
     python tools/bench_generate.py --only none --assistant 4 > profiles/assisted_generate.jsonl
 
 --processors times greedy generate() with repetition_penalty=1.1, no_repeat_ngram_size=3 and one two-token stop sequence that never
@@ -152,6 +160,44 @@ def append_arms(model, Ts, text_len, reps):
                           "chunk_B1_ms_all": [round(v, 3) for v in res["chunk_B1"]],
                           "decode_batch_T_ms_all": [round(v, 3) for v in res["decode_batch_T"]]}), flush=True)
         del c1, cT
+
+
+def extend_arms(model, Ts, text_len, reps, Bs=(1, 8), extend_only=False):
+    """ms per continuation chunk of T tokens over a cache of text_len - 1 + 576 positions: extend path against the piece loop."""
+    g = torch.Generator().manual_seed(0)
+    arms = ("extend",) if extend_only else ("extend", "pieces")
+    for B in Bs:
+        for T in Ts:
+            cache, _ = model._prefill(**prompts(B, text_len), max_new_tokens=T + 1)
+            lens0 = cache.lens.clone()
+            ids = torch.randint(0, 151643, (B, T), generator=g)
+
+            def run(arm):
+                cache.lens.copy_(lens0)                             # the same turn again: the chunk overwrites its own positions
+                model.extend_min_tokens = 17 if arm == "extend" else 1 << 30
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                model._append_chunk(ids, None, cache, "last")
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1)
+
+            res = {a: [] for a in arms}
+            for rep in range(reps + 1):                             # rep 0 warms both arms
+                for a in arms:
+                    ms = run(a)
+                    if rep:
+                        res[a].append(ms)
+            del model.extend_min_tokens
+            rec = {"metric": "continuation_chunk_ms", "B": B, "T": T, "cache_positions": text_len - 1 + 576,
+                   "passes_pieces": (T + 15) // 16}
+            for a in arms:
+                rec[f"{a}_ms"] = round(min(res[a]), 3)
+                rec[f"{a}_ms_all"] = [round(v, 3) for v in res[a]]
+            if not extend_only:
+                rec["speedup"] = round(min(res["pieces"]) / min(res["extend"]), 2)
+            print(json.dumps(rec), flush=True)
+            del cache
 
 
 def assisted_arms(model, k, text_len, reps, n_new=33):
@@ -390,6 +436,9 @@ def main():
     ap.add_argument("--sample-only", default=None, help="comma-separated B of the sampling arms (default 1,8)")
     ap.add_argument("--device-arm-only", action="store_true", help="sampling: skip the torch arm (for a kernel trace)")
     ap.add_argument("--append", default=None, help="comma-separated chunk lengths T: chunk path against the decode path")
+    ap.add_argument("--extend", default=None, help="comma-separated chunk lengths T: extend path against the piece loop, B 1 and 8")
+    ap.add_argument("--extend-only", default=None, help="comma-separated B of the extend arms (default 1,8)")
+    ap.add_argument("--extend-arm-only", action="store_true", help="extend: skip the piece-loop arm (for a kernel trace)")
     ap.add_argument("--assistant", type=int, default=None, help="k: assisted generation (self-draft, student draft) against greedy")
     ap.add_argument("--processors", action="store_true", help="greedy with logits processors: plain / device kernels / torch glue")
     ap.add_argument("--processors-only", default=None, help="comma-separated B of the processor arms (default 1,8)")
@@ -421,6 +470,9 @@ def main():
                           "ms_call_n2": [round(y, 1) for y in t2], "n1": a.n1, "n2": a.n2}), flush=True)
     if a.append:
         append_arms(model, [int(x) for x in a.append.split(",")], a.text_len, a.reps)
+    if a.extend:
+        extend_arms(model, [int(x) for x in a.extend.split(",")], a.text_len, a.reps,
+                    [int(x) for x in a.extend_only.split(",")] if a.extend_only else (1, 8), a.extend_arm_only)
     if a.assistant:
         assisted_arms(model, a.assistant, a.text_len, a.reps)
     if a.speculative:
