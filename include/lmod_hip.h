@@ -331,6 +331,20 @@ int lmod_kv_gather_rows(void* const* dst, const void* const* src, int ntensor, c
  *   (the token stays in [0, V)).  R <= 65535, V >= 2; R == 0 is a no-op. */
 int lmod_sample_bf16(const void* logits, long long ld, int V, const float* u, int R, float temperature, int top_k, float top_p,
                      int chunk, void* ws, long long ws_bytes, int* out_token, float* out_stats, hipStream_t stream);
+/* lmod_sample_rows_bf16 (csrc/sample_rows.hip): lmod_sample_bf16 with the parameters of every row in device arrays of R entries
+ *   (generate_batch with per-request parameters).  greedy[r] == 0: row r's token and stats are bit for bit what lmod_sample_bf16
+ *   returns for that row alone with temperature[r], top_k[r], top_p[r] (same normalisation: T = max(T, 1e-6); top_k <= 0 or >= V: off;
+ *   top_p >= 1: off) - integer masses and one shared weight expression make a row independent of its neighbours, its position and the
+ *   workspace layout.  greedy[r] != 0: the token is lmod_row_argmax_bf16's (the first maximum; +0 and -0 are one value), the stats
+ *   {logsumexp(x) at T = 1, 1, V, -inf}; temperature / top_k / top_p of such a row are not read into the result.
+ *   Launches: always the 6 of the both-filters case, whatever the mix; a workgroup whose row takes no part in a histogram pass returns
+ *   before its first barrier (a function of the row alone: workgroup-uniform).  ws (8-byte aligned): the nh = 3 layout for every row,
+ *   ws_bytes >= R * (64 + 3072 * 3 + 16 * ceil(V / chunk)).  R <= 65535, V >= 2, chunk a multiple of 8; R == 0 is a no-op; the edge
+ *   cases of lmod_sample_bf16 (a sampled row without a finite logit: token 0, lse -inf, kept fraction 0; a greedy one: token 0, lse
+ *   -inf, kept fraction 1). */
+int lmod_sample_rows_bf16(const void* logits, long long ld, int V, const float* u, int R, const float* temperature, const int* top_k,
+                          const float* top_p, const int* greedy, int chunk, void* ws, long long ws_bytes, int* out_token,
+                          float* out_stats, hipStream_t stream);
 
 /* ---- speculative sampling (generate(assistant_model=..., speculative_sampling=True); Leviathan et al. ICML'23, HF's
  *      _speculative_sampling; csrc/specsample.hip) ---------------------------------------------------------------------------
@@ -390,6 +404,20 @@ int lmod_logits_process_bf16(void* logits, long long ld, int V, int R, const int
                              int min_new, int eos, hipStream_t stream);
 int lmod_gen_push_stop(int* tokens, int* done, int* hist, int ld_hist, int* n_hist, const int* n_prompt, int* n_gen, int eos,
                        int pad, const int* stop_flat, const int* stop_off, int n_stop, int R, hipStream_t stream);
+/* The same two with per-row parameters in device arrays of R entries (generate_batch with per-request parameters):
+ * lmod_logits_process_rows_bf16: row r is bit for bit lmod_logits_process_bf16 on that row alone with penalty[r], ngram[r], min_new[r];
+ *   the bad-word table and eos stay per call.  any_penalty: the host's "some penalty[r] != 1" - it requests the V-bit LDS bitmap
+ *   (LMOD_EUNSUPPORTED when it is set and V > 524288); a row with penalty 1 skips the penalty phase.  The caller keeps penalty[r] > 0
+ *   and ngram[r] >= 0 (device arrays are not checked).
+ * lmod_gen_push_stop_rows: lmod_gen_push_stop where row r tests the table's entries [0, n_call) (the call's stop sequences) and
+ *   [stop_first[r], stop_first[r] + stop_count[r]) (its own); the table holds n_table >= n_call sequences (off [n_table + 1]).  A
+ *   range that leaves [0, n_table] is not tested (nothing is clamped). */
+int lmod_logits_process_rows_bf16(void* logits, long long ld, int V, int R, const int* hist, int ld_hist, const int* n_hist,
+                                  const int* n_gen, const float* penalty, const int* ngram, const int* min_new, int any_penalty,
+                                  const int* bad_flat, const int* bad_off, int n_bad, int eos, hipStream_t stream);
+int lmod_gen_push_stop_rows(int* tokens, int* done, int* hist, int ld_hist, int* n_hist, const int* n_prompt, int* n_gen, int eos,
+                            int pad, const int* stop_flat, const int* stop_off, int n_call, int n_table, const int* stop_first,
+                            const int* stop_count, int R, hipStream_t stream);
 
 /* ---- continuous batching (generate_batch(): a finished slot of the running batch is refilled while the others keep decoding;
  *      csrc/batch.hip) -------------------------------------------------------------------------------------------------------
@@ -408,13 +436,17 @@ int lmod_gen_push_stop(int* tokens, int* done, int* hist, int ld_hist, int* n_hi
  *   request outside is skipped as a whole).  Other slots are not touched.  Plain vector stores, no atomics.
  * lmod_request_uniform: u[s] = (w >> 8) * 2^-24 in [0, 1) (24 bits: exact in fp32, never 1), w = word 0 of Philox4x32-10 with counter
  *   (req_id[s], n_gen[s], 0, 0) and key = seed (low word, high word) - the generator of lmod_moe_gate's noise.  A pure function of
- *   (seed, request, token index): independent of the slot, of the requests beside it and of when it was admitted. */
+ *   (seed, request, token index): independent of the slot, of the requests beside it and of when it was admitted.
+ * lmod_request_uniform_rows: the same mapping with counter (ctr0[s], n_gen[s], 0, 0) and key = seed[s] (u64 [B], 8-byte aligned), both
+ *   per slot: a request with a seed of its own runs under (its seed, 0) - the same draws at every list index and in every call - one
+ *   without under (the call's seed, its request index), lmod_request_uniform's stream. */
 int lmod_kv_admit_rows(void* const* dst, const void* const* src, int ntensor, const int* dst_row, const int* lens, int R, int B,
                        int smax_dst, int smax_src, int width, int max_len, hipStream_t stream);
 int lmod_slot_admit(const int* dst_row, const int* prompt_ids, int ld_prompt, const int* n_prompt_new, const int* lens_new,
                     const int* req_new, int R, int B, int* hist, int ld_hist, int* n_prompt, int* n_hist, int* n_gen, int* done,
                     int* cache_lens, int* req_id, hipStream_t stream);
 int lmod_request_uniform(unsigned long long seed, const int* req_id, const int* n_gen, float* u, int B, hipStream_t stream);
+int lmod_request_uniform_rows(const unsigned long long* seed, const int* ctr0, const int* n_gen, float* u, int B, hipStream_t stream);
 
 /* ---- sparse MoE (DeepSpeed 0.9.5 TopKGate/top1gating/top2gating/MOELayer semantics) ------------
  * logits[T,E] = x.float() @ wg^T  (TopKGate.forward; wg kept fp32).

@@ -5,7 +5,9 @@
 //   lmod_slot_admit       - one launch that re-arms the admitted slots' generation state (token history, counters, done flag, cache
 //                           length, request id): the arrays lmod_logits_process_bf16 / lmod_gen_push_stop work on;
 //   lmod_request_uniform  - u[s] in [0, 1) as a pure function of (seed, req_id[s], n_gen[s]) (Philox4x32-10): a request's draws do
-//                           not depend on its slot, its neighbours or the step it was admitted at.
+//                           not depend on its slot, its neighbours or the step it was admitted at;
+//   lmod_request_uniform_rows - the same with the key and the counter's first word per slot (generate_batch with per-request
+//                           parameters: a request with its own seed draws the same numbers in every call and at every list index).
 #include "common.h"
 #include "philox.h"
 
@@ -76,6 +78,19 @@ __global__ __launch_bounds__(BATCH_THREADS) void request_uniform_kernel(unsigned
   u[s] = (float)(c[0] >> 8) * 5.9604644775390625e-08f;
 }
 
+// lmod_request_uniform_rows: key and counter word 0 per slot (a request with a seed of its own: its seed and 0, wherever it stands in
+// the list; one without: the call's seed and its request index).  The same mapping to 24 bits.
+__global__ __launch_bounds__(BATCH_THREADS) void request_uniform_rows_kernel(const unsigned long long* __restrict__ seed,
+                                                                             const int* __restrict__ ctr0, const int* __restrict__ n_gen,
+                                                                             float* __restrict__ u, int B) {
+  const int s = blockIdx.x * BATCH_THREADS + threadIdx.x;
+  if (s >= B) return;
+  const unsigned long long k = seed[s];
+  uint32_t c[4] = {(uint32_t)ctr0[s], (uint32_t)n_gen[s], 0u, 0u};
+  philox4x32_10(c, (uint32_t)k, (uint32_t)(k >> 32));
+  u[s] = (float)(c[0] >> 8) * 5.9604644775390625e-08f;
+}
+
 extern "C" {
 
 int lmod_kv_admit_rows(void* const* dst, const void* const* src, int ntensor, const int* dst_row, const int* lens, int R, int B,
@@ -115,6 +130,15 @@ int lmod_request_uniform(unsigned long long seed, const int* req_id, const int* 
   if (!req_id || !n_gen || !u) return LMOD_EINVAL;
   hipLaunchKernelGGL(request_uniform_kernel, dim3((B + BATCH_THREADS - 1) / BATCH_THREADS), dim3(BATCH_THREADS), 0, stream, seed,
                      req_id, n_gen, u, B);
+  return lmod_launch_status();
+}
+
+int lmod_request_uniform_rows(const unsigned long long* seed, const int* ctr0, const int* n_gen, float* u, int B, hipStream_t stream) {
+  if (B < 0) return LMOD_EINVAL;
+  if (B == 0) return LMOD_OK;
+  if (!seed || !ctr0 || !n_gen || !u || ((uintptr_t)seed & 7)) return LMOD_EINVAL;
+  hipLaunchKernelGGL(request_uniform_rows_kernel, dim3((B + BATCH_THREADS - 1) / BATCH_THREADS), dim3(BATCH_THREADS), 0, stream, seed,
+                     ctr0, n_gen, u, B);
   return lmod_launch_status();
 }
 

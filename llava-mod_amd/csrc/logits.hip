@@ -30,19 +30,21 @@ struct LogitsArgs {
   int min_new, eos, use_bitmap;
 };
 
-__global__ __launch_bounds__(LOGITS_THREADS) void logits_process_kernel(LogitsArgs a) {
-  extern __shared__ uint32_t seen[];                  // V bits: tokens the penalty phase has already handled
-  const int r = blockIdx.x, tid = threadIdx.x;
+// One row by its workgroup.  penalty / ngram / min_new: the row's own; use_bitmap: the launch has the V-bit LDS bitmap and this row's
+// penalty differs from 1.  Everything a branch around a barrier depends on is uniform over the workgroup.
+__device__ __forceinline__ void logits_process_row(const LogitsArgs& a, int r, float penalty, int ngram, int min_new, int use_bitmap,
+                                                   uint32_t* seen) {
+  const int tid = threadIdx.x;
   bf16_t* row = a.x + (long long)r * a.ld;
   const int* h = a.hist + (long long)r * a.ld_hist;
   const int n = min(max(a.n_hist[r], 0), a.ld_hist);
   const int V = a.V;
   // 1. repetition penalty, once per distinct token
-  if (a.use_bitmap && n > 0) {
+  if (use_bitmap && n > 0) {
     const int words = (V + 31) >> 5;
     for (int i = tid; i < words; i += LOGITS_THREADS) seen[i] = 0u;
     __syncthreads();
-    const float p = a.penalty;
+    const float p = penalty;
     for (int i = tid; i < n; i += LOGITS_THREADS) {
       const int t = h[i];
       if (t < 0 || t >= V) continue;
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(LOGITS_THREADS) void logits_process_kernel(LogitsAr
   }
   __syncthreads();
   // 2. no-repeat n-gram: windows that start with the history's last n-1 tokens ban their last token
-  const int g = a.ngram;
+  const int g = ngram;
   if (g > 0 && n >= g) {
     const int* suffix = h + n - (g - 1);
     for (int j = tid; j + g <= n; j += LOGITS_THREADS) {
@@ -76,16 +78,44 @@ __global__ __launch_bounds__(LOGITS_THREADS) void logits_process_kernel(LogitsAr
   }
   __syncthreads();
   // 4. min new tokens
-  if (tid == 0 && a.eos >= 0 && a.eos < V && a.n_gen[r] < a.min_new) row[a.eos] = BF16_NEG_INF;
+  if (tid == 0 && a.eos >= 0 && a.eos < V && a.n_gen[r] < min_new) row[a.eos] = BF16_NEG_INF;
 }
 
-__global__ __launch_bounds__(LOGITS_THREADS) void gen_push_stop_kernel(int* __restrict__ tokens, int* __restrict__ done,
-                                                                        int* __restrict__ hist, int ld_hist, int* __restrict__ n_hist,
-                                                                        const int* __restrict__ n_prompt, int* __restrict__ n_gen,
-                                                                        int eos, int pad, const int* __restrict__ stop_flat,
-                                                                        const int* __restrict__ stop_off, int n_stop, int R) {
-  const int r = blockIdx.x * LOGITS_THREADS + threadIdx.x;
-  if (r >= R) return;
+__global__ __launch_bounds__(LOGITS_THREADS) void logits_process_kernel(LogitsArgs a) {
+  extern __shared__ uint32_t seen[];                  // V bits: tokens the penalty phase has already handled
+  logits_process_row(a, blockIdx.x, a.penalty, a.ngram, a.min_new, a.use_bitmap, seen);
+}
+
+// lmod_logits_process_rows_bf16: penalty / ngram / min_new of row r from device arrays.  a.use_bitmap: the host's "some penalty != 1"
+// (the bitmap is allocated); a row whose own penalty is 1 skips the penalty phase, as the scalar kernel does for penalty == 1.
+__global__ __launch_bounds__(LOGITS_THREADS) void logits_process_rows_kernel(LogitsArgs a, const float* __restrict__ penalty,
+                                                                              const int* __restrict__ ngram,
+                                                                              const int* __restrict__ min_new) {
+  extern __shared__ uint32_t seen[];
+  const int r = blockIdx.x;
+  const float p = penalty[r];
+  logits_process_row(a, r, p, ngram[r], min_new[r], a.use_bitmap && p != 1.0f, seen);
+}
+
+// does the history h[first .. n) of generated tokens end with one of the table's sequences [e0, e1)?
+__device__ __forceinline__ bool stop_match(const int* h, int n, int first, const int* __restrict__ stop_flat,
+                                           const int* __restrict__ stop_off, int e0, int e1) {
+  bool fin = false;
+  for (int e = e0; e < e1 && !fin; ++e) {
+    const int o = stop_off[e], len = stop_off[e + 1] - o;
+    if (len < 1 || n - len < first) continue;
+    bool same = true;
+    for (int q = 0; q < len && same; ++q) same = h[n - len + q] == stop_flat[o + q];
+    fin = same;
+  }
+  return fin;
+}
+
+// One row by one thread: sequences [0, n_stop) of the table, then [own_first, own_first + own_count).
+__device__ __forceinline__ void gen_push_stop_row(int r, int* __restrict__ tokens, int* __restrict__ done, int* __restrict__ hist,
+                                                  int ld_hist, int* __restrict__ n_hist, const int* __restrict__ n_prompt,
+                                                  int* __restrict__ n_gen, int eos, int pad, const int* __restrict__ stop_flat,
+                                                  const int* __restrict__ stop_off, int n_stop, int own_first, int own_count) {
   if (done[r]) { tokens[r] = pad; return; }
   int* h = hist + (long long)r * ld_hist;
   const int t = tokens[r];
@@ -96,14 +126,37 @@ __global__ __launch_bounds__(LOGITS_THREADS) void gen_push_stop_kernel(int* __re
   n_gen[r] += 1;
   const int first = max(n_prompt[r], 0);                  // generated tokens are h[first .. n)
   bool fin = eos >= 0 && t == eos;
-  for (int e = 0; e < n_stop && !fin; ++e) {
-    const int o = stop_off[e], len = stop_off[e + 1] - o;
-    if (len < 1 || n - len < first) continue;
-    bool same = true;
-    for (int q = 0; q < len && same; ++q) same = h[n - len + q] == stop_flat[o + q];
-    fin = same;
-  }
+  if (!fin) fin = stop_match(h, n, first, stop_flat, stop_off, 0, n_stop);
+  if (!fin && own_count > 0) fin = stop_match(h, n, first, stop_flat, stop_off, own_first, own_first + own_count);
   if (fin) done[r] = 1;
+}
+
+__global__ __launch_bounds__(LOGITS_THREADS) void gen_push_stop_kernel(int* __restrict__ tokens, int* __restrict__ done,
+                                                                        int* __restrict__ hist, int ld_hist, int* __restrict__ n_hist,
+                                                                        const int* __restrict__ n_prompt, int* __restrict__ n_gen,
+                                                                        int eos, int pad, const int* __restrict__ stop_flat,
+                                                                        const int* __restrict__ stop_off, int n_stop, int R) {
+  const int r = blockIdx.x * LOGITS_THREADS + threadIdx.x;
+  if (r >= R) return;
+  gen_push_stop_row(r, tokens, done, hist, ld_hist, n_hist, n_prompt, n_gen, eos, pad, stop_flat, stop_off, n_stop, 0, 0);
+}
+
+// lmod_gen_push_stop_rows: row r also tests its own range of the table.  A range that leaves [0, n_table) is not tested at all: no
+// index is clamped.
+__global__ __launch_bounds__(LOGITS_THREADS) void gen_push_stop_rows_kernel(int* __restrict__ tokens, int* __restrict__ done,
+                                                                             int* __restrict__ hist, int ld_hist,
+                                                                             int* __restrict__ n_hist, const int* __restrict__ n_prompt,
+                                                                             int* __restrict__ n_gen, int eos, int pad,
+                                                                             const int* __restrict__ stop_flat,
+                                                                             const int* __restrict__ stop_off, int n_call, int n_table,
+                                                                             const int* __restrict__ stop_first,
+                                                                             const int* __restrict__ stop_count, int R) {
+  const int r = blockIdx.x * LOGITS_THREADS + threadIdx.x;
+  if (r >= R) return;
+  const int f = stop_first[r];
+  int c = stop_count[r];
+  if (f < 0 || c < 0 || f > n_table || c > n_table - f) c = 0;
+  gen_push_stop_row(r, tokens, done, hist, ld_hist, n_hist, n_prompt, n_gen, eos, pad, stop_flat, stop_off, n_call, f, c);
 }
 
 extern "C" {
@@ -127,6 +180,26 @@ int lmod_logits_process_bf16(void* logits, long long ld, int V, int R, const int
   return lmod_launch_status();
 }
 
+int lmod_logits_process_rows_bf16(void* logits, long long ld, int V, int R, const int* hist, int ld_hist, const int* n_hist,
+                                  const int* n_gen, const float* penalty, const int* ngram, const int* min_new, int any_penalty,
+                                  const int* bad_flat, const int* bad_off, int n_bad, int eos, hipStream_t stream) {
+  if (R < 0 || V < 1 || ld < V || ld_hist < 0 || n_bad < 0) return LMOD_EINVAL;
+  if (R == 0) return LMOD_OK;
+  if (!logits || !hist || !n_hist || !n_gen || !penalty || !ngram || !min_new || (n_bad > 0 && (!bad_flat || !bad_off)))
+    return LMOD_EINVAL;
+  LogitsArgs a;
+  a.x = (bf16_t*)logits; a.ld = ld; a.V = V;
+  a.hist = hist; a.ld_hist = ld_hist; a.n_hist = n_hist; a.n_gen = n_gen;
+  a.penalty = 1.0f; a.ngram = 0;
+  a.bad_flat = bad_flat; a.bad_off = bad_off; a.n_bad = n_bad;
+  a.min_new = 0; a.eos = eos;
+  a.use_bitmap = any_penalty != 0;
+  const long long lds = a.use_bitmap ? 4LL * ((V + 31) >> 5) : 0;
+  if (lds > LOGITS_LDS_MAX) return LMOD_EUNSUPPORTED;
+  hipLaunchKernelGGL(logits_process_rows_kernel, dim3(R), dim3(LOGITS_THREADS), (size_t)lds, stream, a, penalty, ngram, min_new);
+  return lmod_launch_status();
+}
+
 int lmod_gen_push_stop(int* tokens, int* done, int* hist, int ld_hist, int* n_hist, const int* n_prompt, int* n_gen, int eos,
                        int pad, const int* stop_flat, const int* stop_off, int n_stop, int R, hipStream_t stream) {
   if (R < 0 || ld_hist < 0 || n_stop < 0) return LMOD_EINVAL;
@@ -134,6 +207,19 @@ int lmod_gen_push_stop(int* tokens, int* done, int* hist, int ld_hist, int* n_hi
   if (!tokens || !done || !hist || !n_hist || !n_prompt || !n_gen || (n_stop > 0 && (!stop_flat || !stop_off))) return LMOD_EINVAL;
   hipLaunchKernelGGL(gen_push_stop_kernel, dim3((R + LOGITS_THREADS - 1) / LOGITS_THREADS), dim3(LOGITS_THREADS), 0, stream, tokens,
                      done, hist, ld_hist, n_hist, n_prompt, n_gen, eos, pad, stop_flat, stop_off, n_stop, R);
+  return lmod_launch_status();
+}
+
+int lmod_gen_push_stop_rows(int* tokens, int* done, int* hist, int ld_hist, int* n_hist, const int* n_prompt, int* n_gen, int eos,
+                            int pad, const int* stop_flat, const int* stop_off, int n_call, int n_table, const int* stop_first,
+                            const int* stop_count, int R, hipStream_t stream) {
+  if (R < 0 || ld_hist < 0 || n_call < 0 || n_table < n_call) return LMOD_EINVAL;
+  if (R == 0) return LMOD_OK;
+  if (!tokens || !done || !hist || !n_hist || !n_prompt || !n_gen || !stop_first || !stop_count ||
+      (n_table > 0 && (!stop_flat || !stop_off))) return LMOD_EINVAL;
+  hipLaunchKernelGGL(gen_push_stop_rows_kernel, dim3((R + LOGITS_THREADS - 1) / LOGITS_THREADS), dim3(LOGITS_THREADS), 0, stream,
+                     tokens, done, hist, ld_hist, n_hist, n_prompt, n_gen, eos, pad, stop_flat, stop_off, n_call, n_table, stop_first,
+                     stop_count, R);
   return lmod_launch_status();
 }
 

@@ -32,22 +32,14 @@
 // Edge cases: -inf logits weigh 0 and are never drawn; a row without a finite logit returns token 0, lse = -inf and kept fraction
 // 0 (no NaN); NaN logits are unspecified (as in beam.hip) but the token stays in [0, V).
 //
-// The device functions (key, weight, scans, selection, the draw of one row) live in sample_common.h: specsample.hip shares them.
+// The device functions (key, weight, scans, selection, the passes' bodies, the draw of one row) live in sample_common.h:
+// specsample.hip and sample_rows.hip (per-row parameters) share them.
 #include "sample_common.h"
 
 // Pass 1: grid (C, R).  Chunk maximum (as a key); the chunk's workgroups also zero the row's header and histograms.
 __global__ __launch_bounds__(256) void sample_max_kernel(SampleArgs a) {
   __shared__ SampleSmem s;
-  const int c = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
-  const bf16_t* row = s_row(a, r);
-  const int lo = c * a.chunk, hi = min(a.V, lo + a.chunk);
-  int k = 0;
-  for_tokens(row, lo, hi, a.vec, tid, [&](uint32_t b, int) { k = max(k, (int)skey(b)); });
-  k = block_max_int(k, &s);
-  if (tid == 0) s_cmax(a, r)[c] = k;
-  const int words = (SAMPLE_HDR_BYTES + a.nh * SAMPLE_HIST_BYTES) / 4, per = (words + a.C - 1) / a.C;
-  uint32_t* z = (uint32_t*)s_hdr(a, r);
-  for (int i = c * per + tid; i < min(words, (c + 1) * per); i += 256) z[i] = 0;
+  sample_pass_max(a, blockIdx.x, blockIdx.y, &s);
 }
 
 // Pass 2: grid (C, R).  mode 0: histogram of the key's high byte over every token -> hist 0.  mode 1: low byte of the tokens in
@@ -56,83 +48,14 @@ __global__ __launch_bounds__(256) void sample_hist_kernel(SampleArgs a, int mode
   __shared__ SampleSmem s;
   __shared__ u64 hm[256];
   __shared__ uint32_t hc[256];
-  const int c = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
-  const bf16_t* row = s_row(a, r);
-  const int lo = c * a.chunk, hi = min(a.V, lo + a.chunk);
-  hm[tid] = 0;
-  hc[tid] = 0;
-  const float m = row_max_value(s_cmax(a, r), a.C, &s);
-  int sel = -1;
-  if (mode == 1) {
-    const Sel k = sel_count(s_hcnt(a, r, 0), s_hmass(a, r, 0), (uint32_t)a.top_k, &s);
-    sel = k.bin;
-    if (c == 0 && tid == 0) {
-      u64* h = s_hdr(a, r);
-      h[H_KSEL] = (u64)k.bin | ((u64)k.c_above << 32); h[H_KMASS] = k.m_above; h[H_TOTAL] = k.total;
-    }
-  } else if (mode == 2) {
-    uint32_t kk = 0, nk = 0;
-    u64 mk = 0;
-    if (a.top_k > 0) resolve_topk(a, r, &s, kk, nk, mk);
-    const double tp = fmin(fmax((double)a.top_p, 0.0), 1.0);
-    const Sel p = sel_mass(s_hcnt(a, r, 0), s_hmass(a, r, 0), a.top_k <= 0, tp, (u64)(tp * (double)mk), 0, (int)(kk >> 8), &s);
-    sel = p.bin;
-    if (c == 0 && tid == 0) {
-      u64* h = s_hdr(a, r);
-      h[H_PSEL] = (u64)kk | ((u64)p.bin << 16) | ((u64)p.c_above << 32); h[H_P] = p.P; h[H_PMASS] = p.m_above;
-      if (a.top_k <= 0) h[H_TOTAL] = p.total;
-    }
-  }
-  __syncthreads();
-  const float T = a.T;
-  for_tokens(row, lo, hi, a.vec, tid, [&](uint32_t b, int) {
-    const uint32_t key = skey(b);
-    uint32_t bin = key >> 8;
-    if (mode != 0) {
-      if ((int)bin != sel) return;
-      bin = key & 255u;
-    }
-    const u64 w = sweight(bf2f((bf16_t)b), m, T);
-    atomicAdd(&hc[bin], 1u);
-    if (w) atomicAdd(&hm[bin], w);
-  });
-  __syncthreads();
-  if (hc[tid]) {
-    atomicAdd(&s_hcnt(a, r, hidx)[tid], hc[tid]);
-    if (hm[tid]) atomicAdd(&s_hmass(a, r, hidx)[tid], hm[tid]);
-  }
+  sample_pass_hist(a, blockIdx.x, blockIdx.y, mode, hidx, &s, hm, hc);
 }
 
 // Pass 3: grid (C, R).  The final cutoff key, then the chunk's kept mass.
 __global__ __launch_bounds__(256) void sample_mass_kernel(SampleArgs a) {
   __shared__ SampleSmem s;
-  const int c = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
-  const bf16_t* row = s_row(a, r);
-  const int lo = c * a.chunk, hi = min(a.V, lo + a.chunk);
-  const float m = row_max_value(s_cmax(a, r), a.C, &s);
-  uint32_t cut = 0, n_kept = (uint32_t)a.V;
-  if (a.use_p) {
-    const u64* h = s_hdr(a, r);
-    const uint32_t kk = (uint32_t)(h[H_PSEL] & 0xffff), B = (uint32_t)((h[H_PSEL] >> 16) & 0xff), above = (uint32_t)(h[H_PSEL] >> 32);
-    const int hidx = a.top_k > 0 ? 2 : 1;
-    const int lb = (a.top_k > 0 && B == (kk >> 8)) ? (int)(kk & 255u) : 0;
-    const Sel p = sel_mass(s_hcnt(a, r, hidx), s_hmass(a, r, hidx), false, 0.0, h[H_P], h[H_PMASS], lb, &s);
-    cut = (B << 8) | (uint32_t)p.bin;
-    n_kept = above + p.c_incl;
-  } else if (a.top_k > 0) {
-    u64 mk;
-    resolve_topk(a, r, &s, cut, n_kept, mk);
-  }
-  if ((a.use_p || a.top_k > 0) && c == 0 && tid == 0) s_hdr(a, r)[H_CUT] = (u64)cut | ((u64)n_kept << 32);
-  const float T = a.T;
-  u64 sum = 0;
-  for_tokens(row, lo, hi, a.vec, tid, [&](uint32_t b, int) {
-    if (skey(b) >= cut) sum += sweight(bf2f((bf16_t)b), m, T);
-  });
-  sum = block_sum_u64(sum, &s);
-  if (tid == 0) s_cmass(a, r)[c] = sum;
+  sample_pass_mass(a, blockIdx.x, blockIdx.y, &s);
 }
-
 
 // Pass 4: one workgroup per row: the draw (sample_common.h) and the stats.
 __global__ __launch_bounds__(256) void sample_draw_kernel(SampleArgs a, const float* __restrict__ u, int* __restrict__ out_token,

@@ -1,7 +1,8 @@
-// What lmod_sample_bf16 (sample.hip) and lmod_spec_sample_bf16 (specsample.hip) share: the 16-bit key of a bf16 logit, the fixed-point
+// What lmod_sample_bf16 (sample.hip), lmod_spec_sample_bf16 (specsample.hip) and lmod_sample_rows_bf16 (sample_rows.hip) share: the 16-bit key of a bf16 logit, the fixed-point
 // weight, the token loops, the 256-thread scans, the radix selection over the row histograms in `ws`, the inverse-CDF draw of one row
 // and the stats record.  The contract, the workspace layout and the reasons are in sample.hip's header comment.  The filter passes
-// themselves (chunk max, histograms, kept mass) are kernels of sample.hip; specsample.hip launches them through sample_launch_filter.
+// themselves (chunk max, histograms, kept mass) are device functions here too (sample_pass_*): sample.hip wraps them in its kernels,
+// which specsample.hip launches through sample_launch_filter; sample_rows.hip calls them with per-row arguments.
 #pragma once
 #include "common.h"
 
@@ -162,6 +163,106 @@ __device__ __forceinline__ void resolve_topk(const SampleArgs& a, int r, SampleS
   key = (hi << 8) | (uint32_t)lo.bin;
   n_kept = above + lo.c_incl;
   mass = h[H_KMASS] + lo.m_incl;
+}
+
+// ---------------------------------------------------------------------------------------------- the filter passes of one workgroup
+// The bodies of sample.hip's kernels as device functions of (a, chunk c, row r): lmod_sample_bf16 / lmod_spec_sample_bf16 call them
+// with the launch's SampleArgs, lmod_sample_rows_bf16 (sample_rows.hip) with a per-row copy.  Every thread of the workgroup calls.
+
+// Pass 1.  Chunk maximum (as a key); the chunk's workgroups also zero the row's header and histograms.
+__device__ __forceinline__ void sample_pass_max(const SampleArgs& a, int c, int r, SampleSmem* sp) {
+  const int tid = threadIdx.x;
+  const bf16_t* row = s_row(a, r);
+  const int lo = c * a.chunk, hi = min(a.V, lo + a.chunk);
+  int k = 0;
+  for_tokens(row, lo, hi, a.vec, tid, [&](uint32_t b, int) { k = max(k, (int)skey(b)); });
+  k = block_max_int(k, sp);
+  if (tid == 0) s_cmax(a, r)[c] = k;
+  const int words = (SAMPLE_HDR_BYTES + a.nh * SAMPLE_HIST_BYTES) / 4, per = (words + a.C - 1) / a.C;
+  uint32_t* z = (uint32_t*)s_hdr(a, r);
+  for (int i = c * per + tid; i < min(words, (c + 1) * per); i += 256) z[i] = 0;
+}
+
+// Pass 2.  mode 0: histogram of the key's high byte over every token -> hist 0.  mode 1: low byte of the tokens in the top-k high
+// bin -> hist 1.  mode 2: low byte of the tokens in the top-p high bin -> hist `hidx`.  hm / hc: 256-entry LDS histograms.
+__device__ __forceinline__ void sample_pass_hist(const SampleArgs& a, int c, int r, int mode, int hidx, SampleSmem* sp, u64* hm,
+                                                 uint32_t* hc) {
+  SampleSmem& s = *sp;
+  const int tid = threadIdx.x;
+  const bf16_t* row = s_row(a, r);
+  const int lo = c * a.chunk, hi = min(a.V, lo + a.chunk);
+  hm[tid] = 0;
+  hc[tid] = 0;
+  const float m = row_max_value(s_cmax(a, r), a.C, &s);
+  int sel = -1;
+  if (mode == 1) {
+    const Sel k = sel_count(s_hcnt(a, r, 0), s_hmass(a, r, 0), (uint32_t)a.top_k, &s);
+    sel = k.bin;
+    if (c == 0 && tid == 0) {
+      u64* h = s_hdr(a, r);
+      h[H_KSEL] = (u64)k.bin | ((u64)k.c_above << 32); h[H_KMASS] = k.m_above; h[H_TOTAL] = k.total;
+    }
+  } else if (mode == 2) {
+    uint32_t kk = 0, nk = 0;
+    u64 mk = 0;
+    if (a.top_k > 0) resolve_topk(a, r, &s, kk, nk, mk);
+    const double tp = fmin(fmax((double)a.top_p, 0.0), 1.0);
+    const Sel p = sel_mass(s_hcnt(a, r, 0), s_hmass(a, r, 0), a.top_k <= 0, tp, (u64)(tp * (double)mk), 0, (int)(kk >> 8), &s);
+    sel = p.bin;
+    if (c == 0 && tid == 0) {
+      u64* h = s_hdr(a, r);
+      h[H_PSEL] = (u64)kk | ((u64)p.bin << 16) | ((u64)p.c_above << 32); h[H_P] = p.P; h[H_PMASS] = p.m_above;
+      if (a.top_k <= 0) h[H_TOTAL] = p.total;
+    }
+  }
+  __syncthreads();
+  const float T = a.T;
+  for_tokens(row, lo, hi, a.vec, tid, [&](uint32_t b, int) {
+    const uint32_t key = skey(b);
+    uint32_t bin = key >> 8;
+    if (mode != 0) {
+      if ((int)bin != sel) return;
+      bin = key & 255u;
+    }
+    const u64 w = sweight(bf2f((bf16_t)b), m, T);
+    atomicAdd(&hc[bin], 1u);
+    if (w) atomicAdd(&hm[bin], w);
+  });
+  __syncthreads();
+  if (hc[tid]) {
+    atomicAdd(&s_hcnt(a, r, hidx)[tid], hc[tid]);
+    if (hm[tid]) atomicAdd(&s_hmass(a, r, hidx)[tid], hm[tid]);
+  }
+}
+
+// Pass 3.  The final cutoff key, then the chunk's kept mass.
+__device__ __forceinline__ void sample_pass_mass(const SampleArgs& a, int c, int r, SampleSmem* sp) {
+  SampleSmem& s = *sp;
+  const int tid = threadIdx.x;
+  const bf16_t* row = s_row(a, r);
+  const int lo = c * a.chunk, hi = min(a.V, lo + a.chunk);
+  const float m = row_max_value(s_cmax(a, r), a.C, &s);
+  uint32_t cut = 0, n_kept = (uint32_t)a.V;
+  if (a.use_p) {
+    const u64* h = s_hdr(a, r);
+    const uint32_t kk = (uint32_t)(h[H_PSEL] & 0xffff), B = (uint32_t)((h[H_PSEL] >> 16) & 0xff), above = (uint32_t)(h[H_PSEL] >> 32);
+    const int hidx = a.top_k > 0 ? 2 : 1;
+    const int lb = (a.top_k > 0 && B == (kk >> 8)) ? (int)(kk & 255u) : 0;
+    const Sel p = sel_mass(s_hcnt(a, r, hidx), s_hmass(a, r, hidx), false, 0.0, h[H_P], h[H_PMASS], lb, &s);
+    cut = (B << 8) | (uint32_t)p.bin;
+    n_kept = above + p.c_incl;
+  } else if (a.top_k > 0) {
+    u64 mk;
+    resolve_topk(a, r, &s, cut, n_kept, mk);
+  }
+  if ((a.use_p || a.top_k > 0) && c == 0 && tid == 0) s_hdr(a, r)[H_CUT] = (u64)cut | ((u64)n_kept << 32);
+  const float T = a.T;
+  u64 sum = 0;
+  for_tokens(row, lo, hi, a.vec, tid, [&](uint32_t b, int) {
+    if (skey(b) >= cut) sum += sweight(bf2f((bf16_t)b), m, T);
+  });
+  sum = block_sum_u64(sum, &s);
+  if (tid == 0) s_cmass(a, r)[c] = sum;
 }
 
 // The draw of one row by its whole workgroup (256 threads, every thread calls): target = floor(u * kept mass); the chunk, then the

@@ -59,13 +59,17 @@ SIGNATURES = {
     "lmod_beam_topk_bf16": "pqi" + "p" + "iii" + "pq" + "ppp" + "p",
     "lmod_kv_gather_rows": "pp" + "i" + "pp" + "iiiii" + "p",
     "lmod_sample_bf16": "pqi" + "pi" + "fif" + "i" + "pq" + "pp" + "p",
+    "lmod_sample_rows_bf16": "pqi" + "pi" + "pppp" + "i" + "pq" + "pp" + "p",
     "lmod_spec_sample_bf16": "pqpqi" + "ppp" + "ii" + "fif" + "i" + "pq" + "pii" + "pp" + "pp" + "p" + "p",
     "lmod_spec_uniform": "Q" + "iiii" + "pi" + "p",
     "lmod_logits_process_bf16": "pqii" + "pipp" + "fi" + "ppi" + "ii" + "p",
     "lmod_gen_push_stop": "pp" + "pipp" + "p" + "ii" + "ppi" + "i" + "p",
+    "lmod_logits_process_rows_bf16": "pqii" + "pipp" + "ppp" + "i" + "ppi" + "i" + "p",
+    "lmod_gen_push_stop_rows": "pp" + "pipp" + "p" + "ii" + "pp" + "ii" + "pp" + "i" + "p",
     "lmod_kv_admit_rows": "pp" + "i" + "pp" + "iiiiii" + "p",
     "lmod_slot_admit": "p" + "pippp" + "ii" + "pipppppp" + "p",
     "lmod_request_uniform": "Q" + "ppp" + "i" + "p",
+    "lmod_request_uniform_rows": "ppp" + "pi" + "p",
     "lmod_moe_router_fwd": "ppp" + "iii" + "p",
     "lmod_moe_gate": "pp" + "iiii" + "pppppppppppppp" + "iQQp" + "p",
     "lmod_moe_combine_fwd": "pppppp" + "ii" + "p",

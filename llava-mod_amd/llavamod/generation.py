@@ -451,7 +451,8 @@ def gen_push_stop(tokens, done, hist, n_hist, n_prompt, n_gen, eos, pad, stops):
 class BatchOutput:
     """`generate_batch(return_dict_in_generate=True)`: sequences (a list, in request order, of 1-D int64 tensors: each request's new
     tokens, cut after its EOS / stop sequence, no padding), token_logprobs (when sampling: a list of fp32 tensors of the same lengths,
-    the log-probability of each drawn token under the warped distribution; None otherwise) and the scheduler's counters:
+    the log-probability of each drawn token under the warped distribution; None otherwise; when a request carries `params`: a list
+    for every request, a greedy token's entry being its log-softmax under the processed logits) and the scheduler's counters:
     num_decode_steps, num_decode_forwards, num_admissions, num_prefills, live_row_steps, total_row_steps, live_fraction."""
 
     def __init__(self, sequences, token_logprobs, scheduler):
@@ -548,7 +549,8 @@ def check_batch_args(requests, max_batch_size=8, max_new_tokens=16, num_beams=1,
                      past_key_values=None):
     """The arguments of `generate_batch` that `generate()` does not have, and the modes it leaves out.  Returns each request's
     max_new_tokens (a list).  ValueError: num_beams > 1, assistant_model, num_return_sequences > 1, past_key_values (out of scope
-    of continuous batching), a bad max_batch_size, a request without `input_ids` or with a budget < 1."""
+    of continuous batching), a bad max_batch_size, a request without `input_ids` or with a budget < 1, a request key other than
+    `input_ids`, `images`, `max_new_tokens` and `params` (a `RequestParams`)."""
     if num_beams != 1:
         raise ValueError("generate_batch does not support num_beams > 1: beam search needs its beams in adjacent rows")
     if assistant_model is not None:
@@ -565,9 +567,12 @@ def check_batch_args(requests, max_batch_size=8, max_new_tokens=16, num_beams=1,
     for i, rq in enumerate(requests):
         if not isinstance(rq, dict) or rq.get("input_ids") is None:
             raise ValueError(f"request {i}: a dict with `input_ids` [S] is expected")
-        unknown = set(rq) - {"input_ids", "images", "max_new_tokens"}
+        unknown = set(rq) - {"input_ids", "images", "max_new_tokens", "params"}
         if unknown:
-            raise ValueError(f"request {i}: unknown keys {sorted(unknown)} (sampling and stop arguments are per call, not per request)")
+            raise ValueError(f"request {i}: unknown keys {sorted(unknown)} (a request's own sampling, processor and stop arguments "
+                             "go into its `params`, a generation.RequestParams)")
+        if rq.get("params") is not None and not isinstance(rq["params"], RequestParams):
+            raise ValueError(f"request {i}: params must be a generation.RequestParams, got {type(rq['params']).__name__}")
         ids = rq["input_ids"]
         if getattr(ids, "dim", lambda: 0)() != 1 or ids.numel() < 1:
             raise ValueError(f"request {i}: input_ids must be a 1-D tensor of at least one token")
@@ -576,3 +581,145 @@ def check_batch_args(requests, max_batch_size=8, max_new_tokens=16, num_beams=1,
             raise ValueError(f"request {i}: max_new_tokens must be an int >= 1, got {m!r}")
         budgets.append(m)
     return budgets
+
+
+# ---------------------------------------------------------------------------------------------- per-request parameters
+class RequestParams:
+    """A request's own decoding arguments for `generate_batch` (the request dict's `params`).  Every field defaults to None = inherit
+    the call's argument of the same name.  stop_sequences apply IN ADDITION to the call's.  seed: the request's k-th uniform is
+    Philox4x32-10 with key = seed at counter (0, k, 0, 0) — the same draws wherever the request stands in the list and whichever call
+    carries it; without one it keeps the call's stream, key = the call's seed at counter (request index, k, 0, 0).  bad_words_ids,
+    suppress_tokens, eos_token_id and pad_token_id stay per call."""
+
+    FIELDS = ("do_sample", "temperature", "top_k", "top_p", "seed", "repetition_penalty", "no_repeat_ngram_size", "min_new_tokens",
+              "stop_sequences")
+
+    def __init__(self, do_sample=None, temperature=None, top_k=None, top_p=None, seed=None, repetition_penalty=None,
+                 no_repeat_ngram_size=None, min_new_tokens=None, stop_sequences=None):
+        self.do_sample, self.temperature, self.top_k, self.top_p, self.seed = do_sample, temperature, top_k, top_p, seed
+        self.repetition_penalty, self.no_repeat_ngram_size, self.min_new_tokens = repetition_penalty, no_repeat_ngram_size, min_new_tokens
+        self.stop_sequences = stop_sequences
+
+    def __repr__(self):
+        return "RequestParams(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS if getattr(self, k) is not None) + ")"
+
+
+class RequestRecord:
+    """One request's effective parameters, as the device sees them: do_sample, temperature (1.0 when greedy), top_k (0: off), top_p
+    (1.0: off), seed (its own, else the call's; None: the call gives none and generate_batch draws it), own_seed and ctr0 (the first
+    counter word: 0 under an own seed, the request index otherwise), penalty, ngram, min_new (0 without an eos_token_id), and its own stop sequences
+    as the range (stop_first, stop_count) of the plan's stop table."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class RequestPlan:
+    """What `check_request_params` made of a call.  per_request: some request carries `params` — False means generate_batch runs the
+    loop and the kernels it ran before per-request parameters existed (`records` is then None).  Otherwise: records (a
+    `RequestRecord` per request), stops (ONE stop table: the call's sequences first, then each request's own), n_call_stops, bad (the
+    call's bad-word table), any_sample / any_process / any_penalty (some request samples / some processor or bad word is active /
+    some repetition penalty differs from 1) and needs_call_seed (a sampled request without a seed of its own)."""
+
+    # rows of the device table [len(TABLE_FIELDS) + 1, max_batch_size] int32 (floats bit-cast); `seed` takes two rows: the B 64-bit
+    # keys as one contiguous u64 [B] array, so slot s's key is the int32 pair (2s, 2s + 1) of those rows
+    TABLE_FIELDS = ("seed", "ctr0", "greedy", "temperature", "top_k", "top_p", "penalty", "ngram", "min_new", "stop_first",
+                    "stop_count")
+    TABLE_ROWS = len(TABLE_FIELDS) + 1
+
+    def __init__(self, per_request, records=None, stops=(), n_call_stops=0, bad=(), any_sample=False, any_process=False,
+                 any_penalty=False, needs_call_seed=False):
+        self.per_request, self.records, self.stops, self.n_call_stops, self.bad = per_request, records, list(stops), n_call_stops, list(bad)
+        self.any_sample, self.any_process, self.any_penalty, self.needs_call_seed = any_sample, any_process, any_penalty, needs_call_seed
+
+    @staticmethod
+    def _f32(x):
+        import struct
+        return struct.unpack("<i", struct.pack("<f", float(x)))[0]
+
+    @classmethod
+    def row_of(cls, field):
+        """First row of `field` in the device table (seed: rows 0 and 1)."""
+        i = cls.TABLE_FIELDS.index(field)
+        return i if i == 0 else i + 1
+
+    @classmethod
+    def neutral_table(cls, B):
+        """The table of B idle slots as a nested list [TABLE_ROWS][B] of int32 values: greedy, temperature 1, no filter, penalty 1, no
+        n-gram, no minimum, no stops."""
+        one = cls._f32(1.0)
+        rows = {"greedy": 1, "temperature": one, "top_p": one, "penalty": one}
+        return [[0] * B, [0] * B] + [[rows.get(f, 0)] * B for f in cls.TABLE_FIELDS[1:]]
+
+    def columns(self, admitted, B, call_seed):
+        """The table entries of the admitted [(request, slot)] as (flat indices into the table viewed as 1-D, int32 values), two
+        equally long lists: one indexed copy writes them."""
+        idx, val = [], []
+        for r, s in admitted:
+            rec = self.records[r]
+            seed = (call_seed if rec.seed is None else rec.seed) or 0
+            seed &= 0xFFFFFFFFFFFFFFFF
+            words = {"ctr0": rec.ctr0, "greedy": int(not rec.do_sample), "temperature": self._f32(rec.temperature), "top_k": rec.top_k,
+                     "top_p": self._f32(rec.top_p), "penalty": self._f32(rec.penalty), "ngram": rec.ngram, "min_new": rec.min_new,
+                     "stop_first": rec.stop_first, "stop_count": rec.stop_count}
+            for half, w in enumerate((seed & 0xFFFFFFFF, seed >> 32)):
+                idx.append(2 * s + half)
+                val.append(w - (1 << 32) if w >= 1 << 31 else w)
+            for f, w in words.items():
+                idx.append(self.row_of(f) * B + s)
+                val.append(int(w))
+        return idx, val
+
+
+def check_request_params(requests, do_sample=False, temperature=1.0, top_k=None, top_p=None, seed=None, repetition_penalty=1.0,
+                         no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0, stop_sequences=None,
+                         stopping_criteria=None, eos_token_id=None, vocab_size=None):
+    """Resolve every request's effective parameters (its `params` over the call's arguments) and check them with the rules of
+    `check_sample_args` and `check_logits_args`; a ValueError names the request.  Host only, once per call.  Returns a `RequestPlan`;
+    when no request carries `params` the plan says so (per_request False) and nothing else is built: the caller's existing checks
+    and path apply unchanged."""
+    if not any(isinstance(rq, dict) and rq.get("params") is not None for rq in requests):
+        return RequestPlan(False)
+    from .kernels import LOGITS_MAX_SEQS
+    call_plan = check_logits_args(repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens,
+                                  stop_sequences, stopping_criteria, eos_token_id, vocab_size)
+    call_stops = list(call_plan.stops) if call_plan is not None else []
+    bad = list(call_plan.bad) if call_plan is not None else []
+    call = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens)
+    records, stops = [], list(call_stops)
+    for i, rq in enumerate(requests):
+        prm = rq.get("params") or RequestParams()
+        if not isinstance(prm, RequestParams):
+            raise ValueError(f"request {i}: params must be a generation.RequestParams, got {type(prm).__name__}")
+        e = {k: (call[k] if getattr(prm, k) is None else getattr(prm, k)) for k in call}
+        try:
+            if e["do_sample"] not in (False, True):
+                raise ValueError(f"do_sample must be False or True, got {e['do_sample']!r}")
+            sd = e["seed"]
+            if sd is not None and (isinstance(sd, bool) or not isinstance(sd, int)):
+                raise ValueError(f"seed must be None or an int, got {sd!r}")
+            check_sample_args(bool(e["do_sample"]), e["temperature"], e["top_k"], e["top_p"], 1)
+            own = check_logits_args(e["repetition_penalty"], e["no_repeat_ngram_size"], None, None, e["min_new_tokens"],
+                                    prm.stop_sequences, None, eos_token_id, vocab_size)
+            own_stops = own.stops if own is not None else []
+            if len(call_stops) + len(own_stops) > LOGITS_MAX_SEQS:
+                raise ValueError(f"stop_sequences: {len(call_stops)} of the call and {len(own_stops)} of the request, at most "
+                                 f"{LOGITS_MAX_SEQS} are supported together")
+        except ValueError as err:
+            raise ValueError(f"request {i}: {err}") from None
+        sample = bool(e["do_sample"])
+        own_seed = prm.seed is not None
+        records.append(RequestRecord(
+            do_sample=sample, temperature=float(e["temperature"]) if sample else 1.0,
+            top_k=(max(0, min(int(e["top_k"]), 2 ** 31 - 1)) if e["top_k"] is not None else 0) if sample else 0,
+            top_p=(float(e["top_p"]) if e["top_p"] is not None else 1.0) if sample else 1.0,
+            seed=(int(sd) & 0xFFFFFFFFFFFFFFFF) if sd is not None else None, own_seed=own_seed, ctr0=0 if own_seed else i,
+            penalty=own.penalty if own is not None else 1.0, ngram=own.ngram if own is not None else 0,
+            min_new=own.min_new if own is not None else 0, stop_first=len(stops) if own_stops else 0, stop_count=len(own_stops)))
+        stops += own_stops
+    return RequestPlan(True, records, stops, len(call_stops), bad,
+                       any_sample=any(r.do_sample for r in records),
+                       any_process=bool(bad) or any(r.penalty != 1.0 or r.ngram > 0 or r.min_new > 0 for r in records),
+                       any_penalty=any(r.penalty != 1.0 for r in records),
+                       needs_call_seed=any(r.do_sample and not r.own_seed for r in records))

@@ -540,6 +540,31 @@ def sample(logits, u, temperature=1.0, top_k=None, top_p=None, stats=False):
     return (tokens, st) if stats else tokens
 
 
+def sample_rows(logits, u, temperature, top_k, top_p, greedy, stats=False, chunk=None):
+    """`sample` with the parameters of every row in device arrays [R] (lmod_sample_rows_bf16): temperature / top_p fp32, top_k /
+    greedy int32 (top_k <= 0 and top_p >= 1 switch a filter off).  A row with greedy == 0 gets exactly `sample`'s token and stats for
+    that row alone under its own parameters; a row with greedy != 0 gets `row_argmax`'s token and the stats {logsumexp of the
+    logits, 1, V, -inf}.  Always six launches.  stats=True also returns fp32 [R, 4].  chunk (a multiple of 8; default: `sample`'s
+    choice): tokens per workgroup — it changes the grid, never a result."""
+    R, V = logits.shape
+    assert logits.dtype == BF16 and logits.stride(1) == 1
+    assert u.dtype == torch.float32 and u.is_cuda and u.is_contiguous() and u.numel() == R
+    for t, dt in ((temperature, torch.float32), (top_k, torch.int32), (top_p, torch.float32), (greedy, torch.int32)):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous() and t.numel() == R
+    tokens = torch.empty(R, device=logits.device, dtype=torch.int32)
+    st = torch.empty((R, 4), device=logits.device, dtype=torch.float32) if stats else None
+    if R == 0:
+        return (tokens, st) if stats else tokens
+    if chunk is None:
+        c_target = max(1, min(-(-384 // R), -(-V // 512)))             # the chunking of `sample`
+        chunk = (-(-V // c_target) + 7) // 8 * 8
+    C = -(-V // chunk)
+    ws = torch.empty(R * (64 + 3072 * 3 + 16 * C), device=logits.device, dtype=torch.uint8)
+    call("lmod_sample_rows_bf16", ptr(logits), logits.stride(0), V, ptr(u), R, ptr(temperature), ptr(top_k), ptr(top_p), ptr(greedy),
+         chunk, ptr(ws), ws.numel(), ptr(tokens), ptr(st))
+    return (tokens, st) if stats else tokens
+
+
 # ------------------------------------------------------------------------------------------ speculative sampling
 def spec_sample(p_logits, q_logits, draft, u_acc, u_draw, done, eos, pad, lens_target, lens_draft, temperature=1.0, top_k=None,
                 top_p=None, stats=False):
@@ -629,6 +654,41 @@ def logits_process_(logits, hist, n_hist, n_gen, penalty=1.0, ngram=0, bad=None,
     return logits
 
 
+def logits_process_rows_(logits, hist, n_hist, n_gen, penalty, ngram, min_new, any_penalty, bad=None, eos=None):
+    """`logits_process_` with penalty (fp32, > 0), ngram and min_new (int32, >= 0) per row in device arrays [R]
+    (lmod_logits_process_rows_bf16); the bad-word table and eos stay per call.  any_penalty: whether some penalty differs from 1 (the
+    host knows; it requests the LDS bitmap).  Row r is exactly `logits_process_` on that row with its own scalars.  Returns logits."""
+    R, V = logits.shape
+    assert logits.dtype == BF16 and logits.is_cuda and logits.stride(1) == 1
+    assert hist.dim() == 2 and hist.shape[0] == R and hist.stride(1) == 1
+    for t in (hist, n_hist, n_gen, ngram, min_new):
+        assert t.dtype == torch.int32 and t.is_cuda
+    assert penalty.dtype == torch.float32 and penalty.is_cuda
+    assert all(t.is_contiguous() and t.numel() == R for t in (n_hist, n_gen, penalty, ngram, min_new))
+    bf, bo, nb = bad if bad is not None else (None, None, 0)
+    rc = call("lmod_logits_process_rows_bf16", ptr(logits), logits.stride(0), V, R, ptr(hist), hist.stride(0), ptr(n_hist), ptr(n_gen),
+              ptr(penalty), ptr(ngram), ptr(min_new), int(bool(any_penalty)), ptr(bf), ptr(bo), nb, -1 if eos is None else int(eos),
+              allow=(_hip.UNSUPPORTED,))
+    if rc:
+        raise ValueError(f"repetition_penalty needs a {V}-bit first-occurrence bitmap in LDS: a vocabulary above 524288 is not supported")
+    return logits
+
+
+def gen_push_stop_rows_(tokens, done, hist, n_hist, n_prompt, n_gen, eos, pad, stop, n_call, stop_first, stop_count):
+    """`gen_push_stop_` where row r tests the first n_call sequences of the stop table (`seq_table` or None) and its own range
+    [stop_first[r], stop_first[r] + stop_count[r]) of it (device int32 [R]; lmod_gen_push_stop_rows)."""
+    R = tokens.numel()
+    for t in (tokens, done, hist, n_hist, n_prompt, n_gen, stop_first, stop_count):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert hist.dim() == 2 and hist.shape[0] == R
+    assert all(t.numel() == R for t in (done, n_hist, n_prompt, n_gen, stop_first, stop_count))
+    sf, so, ns = stop if stop is not None else (None, None, 0)
+    assert 0 <= int(n_call) <= ns
+    call("lmod_gen_push_stop_rows", ptr(tokens), ptr(done), ptr(hist), hist.shape[1], ptr(n_hist), ptr(n_prompt), ptr(n_gen),
+         -1 if eos is None else int(eos), 0 if pad is None else int(pad), ptr(sf), ptr(so), int(n_call), ns, ptr(stop_first),
+         ptr(stop_count), R)
+
+
 def gen_push_stop_(tokens, done, hist, n_hist, n_prompt, n_gen, eos, pad, stop=None):
     """One generation step's bookkeeping on the device (lmod_gen_push_stop), everything int32 and updated in place: a done row's
     token becomes pad; a live row's token is appended to its history and done is set on EOS or when the row's generated tokens end
@@ -695,6 +755,20 @@ def request_uniform(seed, req_id, n_gen, out=None):
     u = torch.empty(B, device=req_id.device, dtype=torch.float32) if out is None else out
     assert u.dtype == torch.float32 and u.is_contiguous() and u.numel() == B
     call("lmod_request_uniform", int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(req_id), ptr(n_gen), ptr(u), B)
+    return u
+
+
+def request_uniform_rows(seed, ctr0, n_gen, out=None):
+    """u [B] fp32 in [0, 1): Philox4x32-10 at counter (ctr0[s], n_gen[s], 0, 0) under the 64-bit key seed[s] (device int64 [B], the
+    key's bit pattern; ctr0 / n_gen device int32 [B]) — `request_uniform` with the key and the first counter word per slot
+    (lmod_request_uniform_rows)."""
+    B = ctr0.numel()
+    for t in (ctr0, n_gen):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == B
+    assert seed.dtype == torch.int64 and seed.is_cuda and seed.is_contiguous() and seed.numel() == B
+    u = torch.empty(B, device=ctr0.device, dtype=torch.float32) if out is None else out
+    assert u.dtype == torch.float32 and u.is_contiguous() and u.numel() == B
+    call("lmod_request_uniform_rows", ptr(seed), ptr(ctr0), ptr(n_gen), ptr(u), B)
     return u
 
 

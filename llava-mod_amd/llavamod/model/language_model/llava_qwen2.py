@@ -613,15 +613,30 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         Philox(seed; request index, k) — the same draw whatever slot the request sits in, whichever requests run beside it and
         whenever it was admitted (`seed` None: drawn from torch's global generator, as generate() does).  The admission prefill is
         not overlapped with decoding: the running slots wait for it.  A MoE model routes the rows of idle slots too (they take expert
-        capacity in a decode step, as the finished rows of a generate() batch do)."""
+        capacity in a decode step, as the finished rows of a generate() batch do).
+
+        Per-request parameters: a request may carry `params`, a `generation.RequestParams` (do_sample, temperature, top_k, top_p,
+        seed, repetition_penalty, no_repeat_ngram_size, min_new_tokens, stop_sequences; None = the call's argument), so that a greedy
+        request and a temperature / top-p request share a batch.  A request's stop_sequences apply in addition to the call's; one
+        with its own seed draws its k-th uniform from Philox(its seed; 0, k) — the same tokens at any list index and in any call;
+        bad_words_ids, suppress_tokens, eos_token_id and pad_token_id stay per call.  Such a call runs `_generate_batch_rows`: the
+        same loop on the per-row kernels, with a fixed launch count per step whatever the mix, and token_logprobs for every request
+        (a greedy token: log-softmax of the processed logits).  A call in which no request has `params` runs the loop below with
+        the kernels it always ran."""
         from ...constants import IMAGE_TOKEN_INDEX
-        from ...generation import BatchOutput, SlotScheduler, check_batch_args, check_logits_args, check_sample_args
+        from ...generation import (BatchOutput, SlotScheduler, check_batch_args, check_logits_args, check_request_params,
+                                   check_sample_args)
         budgets = check_batch_args(requests, max_batch_size, max_new_tokens, num_beams, assistant_model, num_return_sequences,
                                    past_key_values)
         check_sample_args(do_sample, temperature, top_k, top_p, 1)
         V = self.lm_head.weight.shape[0]
         lplan = check_logits_args(repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens,
                                   stop_sequences, stopping_criteria, eos_token_id, V)
+        rplan = check_request_params(requests, do_sample, temperature, top_k, top_p, seed, repetition_penalty, no_repeat_ngram_size,
+                                     bad_words_ids, suppress_tokens, min_new_tokens, stop_sequences, stopping_criteria, eos_token_id, V)
+        if rplan.per_request:
+            return self._generate_batch_rows(rplan, requests, budgets, max_batch_size, eos_token_id, pad_token_id, seed,
+                                             return_dict_in_generate)
         sched = SlotScheduler(budgets, max_batch_size)
         if not requests:
             return BatchOutput([], [] if do_sample else None, sched) if return_dict_in_generate else []
@@ -698,6 +713,96 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
             flat = torch.stack([v for o in lps for v in o]) if sum(n_out) else torch.zeros(0, dtype=torch.int32)
             logprobs = list(flat.view(torch.float32).to(dev).split(n_out))
         return BatchOutput(seqs, logprobs, sched)
+
+    @torch.no_grad()
+    def _generate_batch_rows(self, rplan, requests, budgets, max_batch_size, eos_token_id, pad_token_id, seed, return_dict_in_generate):
+        """generate_batch when some request carries `params` (`rplan`: generation.check_request_params).  The loop, the scheduler, the
+        admission and the state are generate_batch's; the slots' parameters live in one field-major device table [fields, B] int32
+        (floats bit-cast; generation.RequestPlan.TABLE_FIELDS), every field a contiguous [B] array that the per-row kernels read:
+          admit  as generate_batch, then the admitted slots' table entries: one host -> device copy (indices and values), one
+                 indexed copy; a slot that was never admitted holds the neutral values (greedy, penalty 1, no n-gram, no stops);
+          step   lmod_logits_process_rows_bf16 (when any request or the call uses a processor), lmod_request_uniform_rows (when any
+                 request samples), lmod_sample_rows_bf16 (always its six launches: greedy rows are its argmax rows),
+                 lmod_gen_push_stop_rows, the read-back, the decode step.
+        The launches of a step depend on the call (`rplan`'s three flags), never on which requests sit in the slots.  The
+        log-probability of a token: x[t] / T - lse - log(kept fraction) under the row's own warp; a greedy row has T = 1 and keeps
+        everything, so its entry is x[t] - logsumexp(x) of the processed logits."""
+        from ...constants import IMAGE_TOKEN_INDEX
+        from ...generation import BatchOutput, RequestPlan, SlotScheduler
+        sched = SlotScheduler(budgets, max_batch_size)
+        V = self.lm_head.weight.shape[0]
+        B, dev, cfg = max_batch_size, self.model.embed_tokens.weight.device, self.config
+        tower = self.get_image_tower()
+        extra = tower.num_patches - 1 if tower is not None else 0
+        n_ids = [int(rq["input_ids"].numel()) for rq in requests]
+        spliced = [n + (int((rq["input_ids"] == IMAGE_TOKEN_INDEX).sum()) * extra if rq.get("images") is not None else 0)
+                   for n, rq in zip(n_ids, requests)]
+        i32 = dict(device=dev, dtype=torch.int32)
+        st = SimpleNamespace(
+            cache=KVCache(cfg.num_hidden_layers, B, max(s + m for s, m in zip(spliced, budgets)),
+                          cfg.num_key_value_heads * cfg.head_dim, dev),
+            hist=torch.zeros((B, -(-max(n + m for n, m in zip(n_ids, budgets)) // 4) * 4), **i32),
+            n_prompt=torch.zeros(B, **i32), n_hist=torch.zeros(B, **i32), n_gen=torch.zeros(B, **i32),
+            done=torch.ones(B, **i32), req_id=torch.full((B,), -1, **i32),
+            logits=torch.zeros((B, V), device=dev, dtype=BF16))
+        st.tab = K.ptr_table(st.cache.tensors())
+        table = torch.tensor(RequestPlan.neutral_table(B), dtype=torch.int32).to(dev)
+        row = RequestPlan.row_of
+        p_seed = table[0:2].view(-1).view(torch.int64)                                # [B] 64-bit keys
+        p_ctr0, p_greedy, p_topk = table[row("ctr0")], table[row("greedy")], table[row("top_k")]
+        p_temp, p_topp = table[row("temperature")].view(torch.float32), table[row("top_p")].view(torch.float32)
+        p_pen, p_ngram, p_minnew = table[row("penalty")].view(torch.float32), table[row("ngram")], table[row("min_new")]
+        p_first, p_count = table[row("stop_first")], table[row("stop_count")]
+        bad, stop = K.seq_table(rplan.bad, dev), K.seq_table(rplan.stops, dev)
+        pad = eos_token_id if pad_token_id is None else pad_token_id
+        if rplan.needs_call_seed:
+            seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())        # as generate()
+        u = torch.zeros(B, device=dev, dtype=torch.float32)
+        out, lps = [[] for _ in requests], [[] for _ in requests]
+        was_training = self.training
+        self.eval()
+        try:
+            while not sched.finished:
+                admitted = sched.admit()
+                for with_images in (False, True):
+                    group = [(r, s) for r, s in admitted if (requests[r].get("images") is not None) == with_images]
+                    if group:
+                        self._admit(requests, budgets, group, st)
+                if admitted:
+                    cols = torch.tensor(rplan.columns(admitted, B, seed), dtype=torch.int32).to(dev)
+                    table.view(-1)[cols[0]] = cols[1]                      # int32 indices: no cast launch
+                if rplan.any_process:
+                    K.logits_process_rows_(st.logits, st.hist, st.n_hist, st.n_gen, p_pen, p_ngram, p_minnew, rplan.any_penalty, bad,
+                                           eos_token_id)
+                if rplan.any_sample:
+                    K.request_uniform_rows(p_seed, p_ctr0, st.n_gen, out=u)
+                nxt, stats = K.sample_rows(st.logits, u, p_temp, p_topk, p_topp, p_greedy, stats=True)
+                x = st.logits.gather(1, nxt.long()[:, None]).squeeze(1).double() / p_temp.clamp_min(1e-6).double()
+                lp = (x - stats[:, 0].double() - torch.log(stats[:, 1].double())).clamp(max=0.0).float()
+                K.gen_push_stop_rows_(nxt, st.done, st.hist, st.n_hist, st.n_prompt, st.n_gen, eos_token_id, pad, stop,
+                                      rplan.n_call_stops, p_first, p_count)
+                blk = torch.stack([nxt, st.done, lp.view(torch.int32)]).cpu()                 # the step's one read-back
+                live = sched.live
+                for s, r in live.items():
+                    out[r].append(int(blk[0, s]))
+                    lps[r].append(blk[2, s])
+                stopped = [s for s in live if int(blk[1, s]) != 0]
+                by_budget = [s for _, s in sched.step(stopped) if s not in stopped]
+                if by_budget:
+                    flags = blk[1].clone()
+                    flags[by_budget] = 1
+                    st.done.copy_(flags)
+                if sched.live:
+                    st.logits.copy_(self._decode_step(nxt, st.cache))
+                    st.cache.lens.sub_(st.done)
+        finally:
+            self.train(was_training)
+        n_out = [len(o) for o in out]
+        seqs = list(torch.tensor([t for o in out for t in o], dtype=torch.int64).to(dev).split(n_out))
+        if not return_dict_in_generate:
+            return seqs
+        flat = torch.stack([v for o in lps for v in o]) if sum(n_out) else torch.zeros(0, dtype=torch.int32)
+        return BatchOutput(seqs, list(flat.view(torch.float32).to(dev).split(n_out)), sched)
 
     def _admit(self, requests, budgets, group, st):
         """Admission of generate_batch: prefill the requests of `group` ([(request, slot)]) together and move them into their slots
