@@ -448,6 +448,28 @@ int lmod_slot_admit(const int* dst_row, const int* prompt_ids, int ld_prompt, co
 int lmod_request_uniform(unsigned long long seed, const int* req_id, const int* n_gen, float* u, int B, hipStream_t stream);
 int lmod_request_uniform_rows(const unsigned long long* seed, const int* ctr0, const int* n_gen, float* u, int B, hipStream_t stream);
 
+/* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens=k); HF PromptLookupCandidateGenerator; csrc/lookup.hip) -----------
+ * The assisted loop's draft without a second model: the continuation of an earlier occurrence of the row's trailing n-gram in the
+ * row's own history.  All int32 and exact, no atomics, no workspace: two calls give the same output.
+ * lmod_ngram_draft: hist [R, ld_hist] / n_hist [R] / done [R] are the arrays of lmod_logits_process_bf16; the row's pending next token
+ *   is already its last element hist[r, L-1], L = n_hist[r].  1 <= k < T_MAX (16) and 1 <= max_ngram <= 8 (LMOD_EINVAL outside);
+ *   R == 0 is a no-op.  For n = min(max_ngram, L-1) down to 1: the smallest window start i with hist[i:i+n] == hist[L-n:L] and
+ *   i + n < L (a non-empty continuation; the window may overlap the trailing n-gram); the first n that has one wins and the draft is
+ *   hist[i+n : min(i+n+k, L)], cut before its first id outside [0, V).  Ids are compared as plain integers (the negative image
+ *   placeholder can be part of a match) but a placeholder or a pad is never drafted: when the first continuation id is outside
+ *   [0, V) n_draft is 0 and the search does NOT fall through to a shorter n.  A done row, L < 2, L > ld_hist or no match: n_draft 0.
+ *   Outputs: n_draft [R]; draft [R, k]: the draft, then -1 (never equal to a target token, so lmod_spec_accept stops there);
+ *   chunk [R, k+1]: the verification input: the pending token (as stored; 0 when L < 1 or L > ld_hist), the draft, then the pending
+ *   token again (a valid id for the embedding gather; those positions are verified, rejected and rewound like a rejected draft).
+ *   One workgroup per row, one strided pass over the history for all n, a block-wide min-reduction per n.
+ * lmod_hist_push_block: block [R, k+5] is lmod_spec_accept's output; row r's emitted tokens block[r, 0:n_emitted] (n_emitted =
+ *   block[r, k+2]) are appended to hist[r] and n_hist[r] advances, so a live row's history again ends with its pending token
+ *   (next_token is the last emitted one).  n_emitted == 0 (a done row) changes nothing; a row whose emission would pass ld_hist, or
+ *   whose count is outside [0, k+1], is left as it is. */
+int lmod_ngram_draft(const int* hist, int ld_hist, const int* n_hist, const int* done, int R, int k, int max_ngram, int V, int* draft,
+                     int* chunk, int* n_draft, hipStream_t stream);
+int lmod_hist_push_block(const int* block, int k, int* hist, int ld_hist, int* n_hist, int R, hipStream_t stream);
+
 /* ---- sparse MoE (DeepSpeed 0.9.5 TopKGate/top1gating/top2gating/MOELayer semantics) ------------
  * logits[T,E] = x.float() @ wg^T  (TopKGate.forward; wg kept fp32).
  * Experts per layer: 1 <= E <= 32 (`--num_experts`, config/args.py:46); the per-token kernels are instantiated for

@@ -70,6 +70,8 @@ SIGNATURES = {
     "lmod_slot_admit": "p" + "pippp" + "ii" + "pipppppp" + "p",
     "lmod_request_uniform": "Q" + "ppp" + "i" + "p",
     "lmod_request_uniform_rows": "ppp" + "pi" + "p",
+    "lmod_ngram_draft": "pipp" + "iiii" + "ppp" + "p",
+    "lmod_hist_push_block": "pi" + "pip" + "i" + "p",
     "lmod_moe_router_fwd": "ppp" + "iii" + "p",
     "lmod_moe_gate": "pp" + "iiii" + "pppppppppppppp" + "iQQp" + "p",
     "lmod_moe_combine_fwd": "pppppp" + "ii" + "p",

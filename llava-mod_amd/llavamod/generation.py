@@ -262,6 +262,32 @@ def check_spec_sample_args(num_beams, num_assistant_tokens, t_max, num_return_se
     check_sample_args(True, temperature, top_k, top_p, 1)
 
 
+def check_prompt_lookup_args(prompt_lookup_num_tokens, max_matching_ngram_size, t_max, ngram_max, do_sample=False, num_beams=1,
+                             num_return_sequences=1, assistant_model=None, speculative_sampling=False, **unsupported):
+    """Arguments of `generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=n)`: greedy, one sequence per prompt, k in
+    1..t_max-1 (the verification chunk holds k + 1 tokens), n in 1..ngram_max.  ValueError with do_sample, num_beams > 1,
+    num_return_sequences > 1, assistant_model, speculative_sampling, and with any logits-processor or stop-sequence argument
+    (`unsupported`, as name=value) that is not at its default: the loop verifies unprocessed logits, as the assisted loop does."""
+    defaults = {"repetition_penalty": 1.0, "no_repeat_ngram_size": 0, "min_new_tokens": 0}
+    used = [n for n, v in unsupported.items() if v is not None and v != defaults.get(n)]
+    if used:
+        raise ValueError(f"{', '.join(used)} cannot be combined with prompt_lookup_num_tokens: prompt-lookup decoding verifies "
+                         "unprocessed logits")
+    if assistant_model is not None or speculative_sampling:
+        raise ValueError("prompt_lookup_num_tokens drafts from the token history: it cannot be combined with assistant_model or "
+                         "speculative_sampling")
+    if do_sample or num_beams != 1:
+        raise ValueError("prompt_lookup_num_tokens supports greedy decoding only: do_sample=True and num_beams > 1 cannot be "
+                         "combined with it")
+    if num_return_sequences != 1:
+        raise ValueError("prompt-lookup decoding returns one sequence per prompt")
+    k, n = prompt_lookup_num_tokens, max_matching_ngram_size
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= t_max - 1:
+        raise ValueError(f"prompt_lookup_num_tokens must be an int in 1..{t_max - 1}, got {k!r}")
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= ngram_max:
+        raise ValueError(f"max_matching_ngram_size must be an int in 1..{ngram_max}, got {n!r}")
+
+
 def spec_sample_rule(p, q, draft, u_acc, u_draw, done, eos, pad, lens_target, lens_draft):
     """The speculative-sampling rule (Leviathan et al.; HF `_speculative_sampling`) in plain torch — what lmod_spec_sample_bf16 computes
     on the device from logits (the product path calls the kernel; this is the statement the tests hold it against).  p [B, k+1, V] and
@@ -546,15 +572,17 @@ class SlotScheduler:
 
 
 def check_batch_args(requests, max_batch_size=8, max_new_tokens=16, num_beams=1, assistant_model=None, num_return_sequences=1,
-                     past_key_values=None):
+                     past_key_values=None, prompt_lookup_num_tokens=None):
     """The arguments of `generate_batch` that `generate()` does not have, and the modes it leaves out.  Returns each request's
-    max_new_tokens (a list).  ValueError: num_beams > 1, assistant_model, num_return_sequences > 1, past_key_values (out of scope
-    of continuous batching), a bad max_batch_size, a request without `input_ids` or with a budget < 1, a request key other than
+    max_new_tokens (a list).  ValueError: num_beams > 1, assistant_model, prompt_lookup_num_tokens, num_return_sequences > 1,
+    past_key_values (out of scope of continuous batching), a bad max_batch_size, a request without `input_ids` or with a budget < 1, a request key other than
     `input_ids`, `images`, `max_new_tokens` and `params` (a `RequestParams`)."""
     if num_beams != 1:
         raise ValueError("generate_batch does not support num_beams > 1: beam search needs its beams in adjacent rows")
     if assistant_model is not None:
         raise ValueError("generate_batch does not support assistant_model")
+    if prompt_lookup_num_tokens is not None:
+        raise ValueError("generate_batch does not support prompt_lookup_num_tokens: its slots decode one token per step")
     if num_return_sequences != 1:
         raise ValueError("generate_batch returns one sequence per request: num_return_sequences > 1 is not supported "
                          "(list the request more than once)")

@@ -702,6 +702,42 @@ def gen_push_stop_(tokens, done, hist, n_hist, n_prompt, n_gen, eos, pad, stop=N
          -1 if eos is None else int(eos), 0 if pad is None else int(pad), ptr(sf), ptr(so), ns, R)
 
 
+# ------------------------------------------------------------------------------------------ prompt-lookup decoding
+NGRAM_MAX = 8              # csrc/lookup.hip: the longest trailing n-gram lmod_ngram_draft looks up
+
+
+def ngram_draft(hist, n_hist, done, k, max_ngram, V, out=None):
+    """The prompt-lookup draft of every row from its own history (lmod_ngram_draft in include/lmod_hip.h).  hist [R, L] / n_hist [R] /
+    done [R]: device int32, the history already ending with the row's pending token.  Returns (draft [R, k]: the draft then -1,
+    chunk [R, k+1]: pending token, draft, pending token again, n_draft [R]); out: the three tensors to reuse.  k outside
+    1..APPEND_T_MAX-1 or max_ngram outside 1..NGRAM_MAX raises (LMOD_EINVAL)."""
+    R = hist.shape[0]
+    for t in (hist, n_hist, done):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert hist.dim() == 2 and n_hist.numel() == R and done.numel() == R
+    k = int(k)
+    if out is None:
+        out = (torch.empty((R, max(k, 0)), device=hist.device, dtype=torch.int32),
+               torch.empty((R, max(k, 0) + 1), device=hist.device, dtype=torch.int32),
+               torch.empty(R, device=hist.device, dtype=torch.int32))
+    draft, chunk, n_draft = out
+    assert all(t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() for t in out)
+    assert (k < 1 or (tuple(draft.shape) == (R, k) and tuple(chunk.shape) == (R, k + 1))) and n_draft.numel() == R
+    call("lmod_ngram_draft", ptr(hist), hist.shape[1], ptr(n_hist), ptr(done), R, k, int(max_ngram), int(V), ptr(draft), ptr(chunk),
+         ptr(n_draft))
+    return draft, chunk, n_draft
+
+
+def hist_push_block_(block, k, hist, n_hist):
+    """Append every row's emitted tokens of one assisted round (block [R, k+5] int32, `spec_accept`'s layout) to its history, in
+    place (lmod_hist_push_block): hist [R, L] and n_hist [R] device int32; a row that would overflow L is left as it is."""
+    R = hist.shape[0]
+    for t in (block, hist, n_hist):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert hist.dim() == 2 and tuple(block.shape) == (R, int(k) + 5) and n_hist.numel() == R
+    call("lmod_hist_push_block", ptr(block), int(k), ptr(hist), hist.shape[1], ptr(n_hist), R)
+
+
 # ------------------------------------------------------------------------------------------ continuous batching
 def _distinct_slots(dst_row, B):
     """dst_row: a host list of slot numbers — the kernels trust it, so it is checked here."""

@@ -370,7 +370,8 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                  num_return_sequences=1, length_penalty=1.0, early_stopping=False, return_dict_in_generate=False,
                  past_key_values=None, assistant_model=None, num_assistant_tokens=5, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0, stop_sequences=None,
-                 stopping_criteria=None, speculative_sampling=False, **kwargs):
+                 stopping_criteria=None, speculative_sampling=False, prompt_lookup_num_tokens=None, max_matching_ngram_size=2,
+                 **kwargs):
         """Generation with a KV cache (the reference's eval path calls HF `generate` on the Eval model,
         llava_qwen2_moe.py:629-681; its serving code passes do_sample / temperature / top_p, its eval scripts num_beams).
         Greedy by default; do_sample=True draws from the temperature / top-k / top-p filtered distribution (`seed` makes the
@@ -399,6 +400,15 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         speculative_sampling=True without assistant_model raises ValueError.  assistant_model with do_sample=True still raises the
         greedy-only error: folding this mode into do_sample=True is left to a later change that may touch the tests pinning it.
 
+        prompt_lookup_num_tokens = k (1..APPEND_T_MAX-1; HF's name) with max_matching_ngram_size (1..kernels.NGRAM_MAX, HF's default
+        2): greedy prompt-lookup decoding, `_prompt_lookup_generate` - the assisted loop without an assistant: every round drafts up
+        to k tokens from the continuation of an earlier occurrence of the row's trailing n-gram in its own token history
+        (lmod_ngram_draft) and verifies them in one pass.  The tokens are plain greedy's away from argmax ties.  Works with images
+        and past_key_values; the history is THIS call's input_ids plus what it generates, earlier turns' tokens are not in it.
+        Greedy only, one sequence per prompt; with do_sample, num_beams > 1, num_return_sequences > 1, assistant_model,
+        speculative_sampling, a logits processor or a stop argument it raises ValueError.  A call without the argument runs the
+        code it ran before.
+
         Logits processors and stop sequences (HF names and semantics, transformers 5.x; greedy and sampling only — with
         num_beams > 1 or assistant_model any of them raises ValueError), applied on the device every step by
         lmod_logits_process_bf16, in this order, before the token is selected:
@@ -420,6 +430,16 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         sequences of at most kernels.LOGITS_MAX_SEQ_LEN tokens per table, ids in [0, V).  A call that uses none of these arguments
         runs the loop below exactly as before."""
         from ...generation import check_logits_args
+        if prompt_lookup_num_tokens is not None:
+            from ...generation import check_prompt_lookup_args
+            check_prompt_lookup_args(prompt_lookup_num_tokens, max_matching_ngram_size, K.APPEND_T_MAX, K.NGRAM_MAX, do_sample, num_beams,
+                                     num_return_sequences, assistant_model, speculative_sampling,
+                                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                     bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens, min_new_tokens=min_new_tokens,
+                                     stop_sequences=stop_sequences, stopping_criteria=stopping_criteria)
+            return self._prompt_lookup_generate(input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id,
+                                                prompt_lookup_num_tokens, max_matching_ngram_size, return_dict_in_generate,
+                                                past_key_values)
         if speculative_sampling:
             from ...generation import check_spec_sample_args
             if assistant_model is None:
@@ -582,7 +602,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                        temperature=1.0, top_k=None, top_p=None, seed=None, num_beams=1, num_return_sequences=1,
                        return_dict_in_generate=False, past_key_values=None, assistant_model=None, repetition_penalty=1.0,
                        no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0, stop_sequences=None,
-                       stopping_criteria=None):
+                       stopping_criteria=None, prompt_lookup_num_tokens=None):
         """Greedy / sampling generation over a LIST of requests with continuous batching: `max_batch_size` slots decode together and
         a slot whose request has ended (EOS, a stop sequence, its max_new_tokens) is refilled with the next request's freshly
         prefilled prompt before the next step, while the other slots keep decoding — `generate()` over a batch runs every row until
@@ -592,7 +612,8 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         optional `max_new_tokens` (default: the call's).  The greedy and sampling arguments of `generate()` apply to the whole call,
         with the same checks and semantics (eos_token_id, pad_token_id, do_sample / temperature / top_k / top_p / seed,
         stop_sequences / stopping_criteria, repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens,
-        min_new_tokens); num_beams > 1, assistant_model, num_return_sequences > 1 and past_key_values raise ValueError.  Returns a
+        min_new_tokens); num_beams > 1, assistant_model, prompt_lookup_num_tokens, num_return_sequences > 1 and past_key_values raise
+        ValueError.  Returns a
         list, in request order, of 1-D int64 tensors: each request's new tokens, cut after its EOS / stop sequence, no padding; with
         return_dict_in_generate a `BatchOutput` (sequences, token_logprobs when sampling, the scheduler's counters).
 
@@ -627,7 +648,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         from ...generation import (BatchOutput, SlotScheduler, check_batch_args, check_logits_args, check_request_params,
                                    check_sample_args)
         budgets = check_batch_args(requests, max_batch_size, max_new_tokens, num_beams, assistant_model, num_return_sequences,
-                                   past_key_values)
+                                   past_key_values, prompt_lookup_num_tokens)
         check_sample_args(do_sample, temperature, top_k, top_p, 1)
         V = self.lm_head.weight.shape[0]
         lplan = check_logits_args(repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens,
@@ -915,6 +936,84 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         seq = book.sequences().to(dev)
         if return_dict_in_generate:
             return AssistedOutput(seq, book.num_rounds, 1 + book.num_rounds, book.num_accepted.to(dev), tcache)
+        return seq
+
+    @torch.no_grad()
+    def _prompt_lookup_generate(self, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, k, max_ngram,
+                                return_dict_in_generate, past=None):
+        """Greedy prompt-lookup decoding, HF `generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=max_ngram)`: the assisted
+        loop whose draft is the row's own token history, so there is no second model, no draft cache and no catch-up.  The history
+        [B, S + max_new_tokens + k + 1] lives on the device as `_processed_generate` builds it: this call's `input_ids`, live tokens
+        only (right-padded; ids as given, an image placeholder is one negative id), then the first argmax and whatever is emitted.
+        With `past` the earlier turns' tokens are NOT in it: only this turn can be looked up.  Per round, always the same launches:
+        (1) lmod_ngram_draft (draft, verification chunk); (2) the chunk's embeddings; (3) ONE forward_append with T = k + 1 for every
+        row, whether it has a draft or not; (4) the head; (5) lmod_row_argmax_bf16; (6) lmod_spec_accept (the -1 behind a short draft
+        never matches, the repeated pending token behind it is rejected and rewound like any rejected draft; `lens_draft` is a
+        scratch nothing reads); (7) lmod_hist_push_block; (8) the round's one read-back, the [B, k+5] block.  The host never asks
+        whether a draft exists.  A sample the host stops at max_new_tokens is marked done on the device; after every round the
+        cache's lens are set from the host's count to prompt + emitted tokens - 1 (the device's value wherever the round was not cut
+        by EOS or max_new_tokens), so a finished row rewrites the same dead positions while the others go on and the returned cache
+        holds, as plain greedy's does, the prompt and every returned token but each row's last.  The result equals plain greedy
+        wherever the chunk and the decode path agree on the argmax (away from ties).  A MoE model routes the B * (k+1) rows of a
+        round with the eval capacity rule over the rows of that call.  `assisted_trace` (measurement only) receives 4 events per
+        round: start, after the draft, after the verification pass and its argmax, after accept / push / read-back;
+        `assisted_force_accept` (measurement only) counts every drafted token as accepted.  Returns the new tokens
+        [B, <= max_new_tokens]; with return_dict_in_generate an `AssistedOutput`."""
+        from ...generation import AssistedBookkeeper, AssistedOutput
+        was_training = self.training
+        self.eval()
+        try:
+            cache, logits = self._start(input_ids, attention_mask, images, max_new_tokens + k + 1, past)
+            B, dev = logits.shape[0], logits.device
+            V = logits.shape[1]
+            book = AssistedBookkeeper(B, k, max_new_tokens, eos_token_id, eos_token_id if pad_token_id is None else pad_token_id)
+            nxt = K.row_argmax(logits)
+            done = book.first(nxt).to(device=dev, dtype=torch.int32).contiguous()
+            ids = input_ids.to(device=dev, dtype=torch.int32)
+            S = ids.shape[1]
+            n_prompt = (attention_mask.to(dev).to(torch.int32).sum(1) if attention_mask is not None
+                        else torch.full((B,), S, device=dev, dtype=torch.int32))
+            hist = torch.zeros((B, S + max_new_tokens + k + 1), device=dev, dtype=torch.int32)
+            hist[:, :S] = ids
+            hist.scatter_(1, n_prompt.long()[:, None], nxt[:, None])                   # the pending token ends the history
+            n_hist = (n_prompt + 1).to(torch.int32).contiguous()
+            len0 = cache.lens.cpu().long()                                              # cache positions before the first new token
+            lt_h = len0.clone()
+            emb_w = self.model.embed_tokens.weight
+            bufs = (torch.empty((B, k), device=dev, dtype=torch.int32), torch.empty((B, k + 1), device=dev, dtype=torch.int32),
+                    torch.empty(B, device=dev, dtype=torch.int32))
+            lens_scratch = torch.zeros(B, device=dev, dtype=torch.int32)
+            force = getattr(self, "assisted_force_accept", False)
+            trace = getattr(self, "assisted_trace", None)
+            mark = (lambda: None) if trace is None else (lambda: (ev.append(torch.cuda.Event(enable_timing=True)), ev[-1].record()))
+            while not book.finished:
+                ev = []
+                mark()
+                draft_t, chunk, _ = K.ngram_draft(hist, n_hist, done, k, max_ngram, V, out=bufs)
+                mark()
+                if int(lt_h.max()) + k + 1 > cache.smax:
+                    cache.grow(int(lt_h.max()) + k + 1 + max_new_tokens)
+                hid = self.model.forward_append(K.gather_rows(emb_w, None, chunk.view(-1), emb_w.shape[1]), cache, k + 1,
+                                                max_len=int(lt_h.max()))
+                target = K.row_argmax(ops.linear_fwd(hid, self.head())).view(B, k + 1)
+                mark()
+                if force:                                                               # measurement only; the -1 fill stays a mismatch
+                    target[:, :k] = torch.where(draft_t >= 0, draft_t, target[:, :k])
+                block, nxt = K.spec_accept(draft_t, target, done, eos_token_id, book.pad, cache.lens, lens_scratch)
+                K.hist_push_block_(block, k, hist, n_hist)
+                book.update(block.cpu())                                                # the round's one read-back
+                mark()
+                if trace is not None:
+                    trace.append(ev)
+                # host -> device only: rows the host stopped are done, and every row's cache length is what the host counts
+                done.copy_(book.stopped.to(torch.int32))
+                lt_h = len0 + book.n - 1
+                cache.lens.copy_(lt_h.to(torch.int32))
+        finally:
+            self.train(was_training)
+        seq = book.sequences().to(dev)
+        if return_dict_in_generate:
+            return AssistedOutput(seq, book.num_rounds, 1 + book.num_rounds, book.num_accepted.to(dev), cache)
         return seq
 
     @torch.no_grad()

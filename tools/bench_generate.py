@@ -56,6 +56,14 @@ beside the measured wall time.  One JSON line.
 
     python tools/bench_generate.py --only none --speculative 5 > profiles/spec_sample_ab.jsonl
     rocprofv3 --kernel-trace --stats -- python tools/bench_generate.py --spec-kernel-only 5
+
+--lookup k times generate(prompt_lookup_num_tokens=k) (prompt-lookup decoding: the draft is the call's own token history) against plain
+greedy at B in {1, 8}, three arms alternating call by call in one process, best of --reps: greedy, lookup (random weights: what the
+history happens to offer is all that is accepted) and lookup_forced (model.assisted_force_accept: every drafted token counts as
+accepted; its tokens are not greedy's).  Every round is split into draft / verify / accept by events inside the loop
+(model.assisted_trace).  One JSON line per B.
+
+    python tools/bench_generate.py --only none --lookup 4 > profiles/prompt_lookup.jsonl
 """
 import argparse
 import json
@@ -245,6 +253,48 @@ def assisted_arms(model, k, text_len, reps, n_new=33):
     rec.update({f"{a}_{n}": v for a, st in stats.items() for n, v in st.items()})
     rec.update({f"{a}_round_ms": ph for a, ph in phases.items()})
     print(json.dumps(rec), flush=True)
+
+
+def lookup_arms(model, k, text_len, reps, Bs=(1, 8), n_new=33, max_ngram=2):
+    """ms per call and per emitted token of plain greedy and of the prompt-lookup loop, B 1 and 8 (see the module docstring)."""
+    for B in Bs:
+        pr = prompts(B, text_len)
+
+        def run(lookup):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            kw = dict(prompt_lookup_num_tokens=k, max_matching_ngram_size=max_ngram, return_dict_in_generate=True) if lookup else {}
+            e0.record()
+            out = model.generate(**pr, max_new_tokens=n_new, **kw)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1), out
+
+        arms = {"greedy": (False, False), "lookup": (True, False), "lookup_forced": (True, True)}
+        res, stats, phases = {a: [] for a in arms}, {}, {}
+        for rep in range(reps + 1):                                # rep 0 warms every arm
+            for a, (lookup, forced) in arms.items():
+                model.assisted_force_accept = forced
+                model.assisted_trace = [] if lookup else None
+                ms, out = run(lookup)
+                if rep:
+                    res[a].append(ms)
+                if lookup:
+                    stats[a] = dict(rounds=out.num_rounds, accepted=int(out.num_accepted.sum()), tokens=int(out.sequences.shape[1]))
+                    tr = model.assisted_trace
+                    phases[a] = {n: round(sum(ev[i].elapsed_time(ev[i + 1]) for ev in tr) / max(1, len(tr)), 3)
+                                 for i, n in enumerate(("draft", "verify", "accept"))}
+        del model.assisted_force_accept, model.assisted_trace
+        # the prefill is inside the per-call figures; the per-round phases are device time between events recorded inside the loop
+        # (draft: lmod_ngram_draft; verify: embedding gather, forward_append, head, argmax; accept: lmod_spec_accept,
+        # lmod_hist_push_block, the round's one read-back and the host bookkeeping)
+        rec = {"metric": "prompt_lookup_ms_per_call", "B": B, "k": k, "max_ngram": max_ngram, "new_tokens": n_new,
+               "prompt_positions": text_len - 1 + 576}
+        for a in arms:
+            rec[f"{a}_ms"] = round(min(res[a]), 2)
+            rec[f"{a}_ms_all"] = [round(v, 2) for v in res[a]]
+        rec.update({f"{a}_{n}": v for a, st in stats.items() for n, v in st.items()})
+        rec.update({f"{a}_round_ms": ph for a, ph in phases.items()})
+        print(json.dumps(rec), flush=True)
 
 
 def speculative_arms(model, k, text_len, reps, Bs=(1, 8), n_new=33, sample=dict(temperature=1.0, top_p=0.9)):
@@ -445,6 +495,7 @@ def main():
     ap.add_argument("--batched", type=int, default=None, help="N requests: generate_batch against static batches and a B = 1 loop")
     ap.add_argument("--max-batch-size", type=int, default=8, help="slots of the --batched arms")
     ap.add_argument("--speculative", type=int, default=None, help="k: speculative sampling (student draft / forced) against do_sample")
+    ap.add_argument("--lookup", type=int, default=None, help="k: prompt-lookup decoding (as is / acceptance forced) against greedy")
     ap.add_argument("--spec-kernel-only", type=int, default=None, help="k: lmod_spec_sample_bf16 alone, no model (for a kernel trace)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate.py measures on the GPU"
@@ -475,6 +526,8 @@ def main():
                     [int(x) for x in a.extend_only.split(",")] if a.extend_only else (1, 8), a.extend_arm_only)
     if a.assistant:
         assisted_arms(model, a.assistant, a.text_len, a.reps)
+    if a.lookup:
+        lookup_arms(model, a.lookup, a.text_len, a.reps)
     if a.speculative:
         speculative_arms(model, a.speculative, a.text_len, a.reps)
     if a.batched:
