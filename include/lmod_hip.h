@@ -470,6 +470,37 @@ int lmod_ngram_draft(const int* hist, int ld_hist, const int* n_hist, const int*
                      int* chunk, int* n_draft, hipStream_t stream);
 int lmod_hist_push_block(const int* block, int k, int* hist, int ld_hist, int* n_hist, int R, hipStream_t stream);
 
+/* ---- prompt-lookup decoding under continuous batching (generate_batch(prompt_lookup_num_tokens=k); csrc/batch_lookup.hip) --------
+ * The round bookkeeping of a batch whose slots are admitted, run and ended independently; it does not depend on where the draft came
+ * from.  Slot state (all int32 [B] unless noted): done, hist [B, ld_hist], n_hist, n_prompt, n_gen - the arrays of lmod_slot_admit and
+ * lmod_gen_push_stop - and budget (the slot's request's max_new_tokens, >= 1).  The stop table is lmod_gen_push_stop's (stop_flat,
+ * stop_off [n_stop + 1]) and so is the test (csrc/stop_match.h): the slot's last len tokens equal a sequence of length len and all of
+ * them were generated (n_hist - len >= n_prompt), whichever round emitted them.  A token ENDS a slot when it is eos (eos >= 0), or
+ * completes a stop sequence, or brings n_gen to budget.  Both: one thread per slot, exact, no atomics, no workspace; every index
+ * is checked and none clamped; B == 0 is a no-op; a null pointer (the stop table only when n_stop > 0) is LMOD_EINVAL.
+ * lmod_batch_lookup_first: the first token of freshly admitted slots.  tokens [B]: the argmax of the slots' logits rows.  A slot is
+ *   FRESH when done == 0 && n_gen == 0.  Fresh: tokens[s] is appended to the history (n_hist + 1), n_gen = 1, first_tok[s] =
+ *   tokens[s], done[s] = 1 when the token ends the slot.  Any other slot: first_tok[s] = -1 and nothing else is touched.  The cache
+ *   length is not an argument: the pending token is not in the cache.  A fresh slot whose history row is full (n_hist >= ld_hist) is
+ *   left as it is and marked done, first_tok -1.
+ * lmod_batch_lookup_round: acceptance, emission and every end condition of one round.  draft [B, k] (lmod_ngram_draft's: the draft,
+ *   then -1), target [B, k+1] (the argmax of the k+1 verification rows), first_tok [B] (above), cache_lens [B] as the verification pass
+ *   left them, L0 + k + 1.  1 <= k < T_MAX (16), LMOD_EINVAL outside.  Output block [B, k+6]: columns 0..k the emitted tokens then
+ *   pad, k+1 n_acc, k+2 n_emit, k+3 the next pending token (pad when fin), k+4 fin, k+5 first_tok[s].
+ *   A slot done at entry: tokens pad, n_acc = n_emit = 0, next = pad, fin = 1, cache_lens[s] = L0 (an idle slot stays where it is
+ *   however many rounds pass); history and n_gen untouched.  A live slot: n_acc = the longest prefix with draft[j] == target[j]; the
+ *   candidates draft[0 .. n_acc) then target[n_acc] are emitted in order - appended to the history, n_gen and n_emit advance - and
+ *   emission stops after a candidate that ends the slot (fin = 1; otherwise all n_acc + 1 are emitted and fin = 0); done[s] = fin;
+ *   cache_lens[s] = L0 + n_emit: the cache holds the prompt and every emitted token but the last, plain greedy's invariant (the next
+ *   pending token is the last one emitted).  A history row that fills up stops the emission there and ends the slot; cache_lens below
+ *   k + 1 (no verification pass left them) ends the slot and is not written. */
+int lmod_batch_lookup_first(const int* tokens, int* done, int* hist, int ld_hist, int* n_hist, const int* n_prompt, int* n_gen,
+                            const int* budget, int eos, const int* stop_flat, const int* stop_off, int n_stop, int* first_tok, int B,
+                            hipStream_t stream);
+int lmod_batch_lookup_round(const int* draft, const int* target, const int* first_tok, int k, int* done, int* hist, int ld_hist,
+                            int* n_hist, const int* n_prompt, int* n_gen, const int* budget, int* cache_lens, int eos, int pad,
+                            const int* stop_flat, const int* stop_off, int n_stop, int* block, int B, hipStream_t stream);
+
 /* ---- sparse MoE (DeepSpeed 0.9.5 TopKGate/top1gating/top2gating/MOELayer semantics) ------------
  * logits[T,E] = x.float() @ wg^T  (TopKGate.forward; wg kept fp32).
  * Experts per layer: 1 <= E <= 32 (`--num_experts`, config/args.py:46); the per-token kernels are instantiated for

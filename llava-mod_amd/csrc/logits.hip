@@ -17,6 +17,7 @@
 // lmod_gen_push_stop is the per-step bookkeeping of the same loop: one thread per row appends the step's token to the history and
 // decides whether the row is done (EOS or a stop sequence over the GENERATED tokens only).
 #include "common.h"
+#include "stop_match.h"
 
 #define LOGITS_THREADS 256
 #define LOGITS_LDS_MAX 65536
@@ -95,20 +96,6 @@ __global__ __launch_bounds__(LOGITS_THREADS) void logits_process_rows_kernel(Log
   const int r = blockIdx.x;
   const float p = penalty[r];
   logits_process_row(a, r, p, ngram[r], min_new[r], a.use_bitmap && p != 1.0f, seen);
-}
-
-// does the history h[first .. n) of generated tokens end with one of the table's sequences [e0, e1)?
-__device__ __forceinline__ bool stop_match(const int* h, int n, int first, const int* __restrict__ stop_flat,
-                                           const int* __restrict__ stop_off, int e0, int e1) {
-  bool fin = false;
-  for (int e = e0; e < e1 && !fin; ++e) {
-    const int o = stop_off[e], len = stop_off[e + 1] - o;
-    if (len < 1 || n - len < first) continue;
-    bool same = true;
-    for (int q = 0; q < len && same; ++q) same = h[n - len + q] == stop_flat[o + q];
-    fin = same;
-  }
-  return fin;
 }
 
 // One row by one thread: sequences [0, n_stop) of the table, then [own_first, own_first + own_count).

@@ -72,6 +72,8 @@ SIGNATURES = {
     "lmod_request_uniform_rows": "ppp" + "pi" + "p",
     "lmod_ngram_draft": "pipp" + "iiii" + "ppp" + "p",
     "lmod_hist_push_block": "pi" + "pip" + "i" + "p",
+    "lmod_batch_lookup_first": "p" + "ppippp" + "p" + "i" + "ppi" + "pi" + "p",
+    "lmod_batch_lookup_round": "ppp" + "i" + "ppippp" + "pp" + "ii" + "ppi" + "pi" + "p",
     "lmod_moe_router_fwd": "ppp" + "iii" + "p",
     "lmod_moe_gate": "pp" + "iiii" + "pppppppppppppp" + "iQQp" + "p",
     "lmod_moe_combine_fwd": "pppppp" + "ii" + "p",

@@ -479,13 +479,20 @@ class BatchOutput:
     tokens, cut after its EOS / stop sequence, no padding), token_logprobs (when sampling: a list of fp32 tensors of the same lengths,
     the log-probability of each drawn token under the warped distribution; None otherwise; when a request carries `params`: a list
     for every request, a greedy token's entry being its log-softmax under the processed logits) and the scheduler's counters:
-    num_decode_steps, num_decode_forwards, num_admissions, num_prefills, live_row_steps, total_row_steps, live_fraction."""
+    num_decode_steps, num_decode_forwards, num_admissions, num_prefills, live_row_steps, total_row_steps, live_fraction.  A call with
+    prompt_lookup_num_tokens (a `LookupSlotScheduler`) additionally carries num_rounds, num_target_forwards (one verification pass per
+    round; admission prefills are counted by num_prefills, not here) and num_accepted (a list, in request order: the draft tokens that
+    were emitted, min(n_acc, n_emitted) per round, `AssistedBookkeeper`'s count); its num_decode_steps and num_decode_forwards are 0
+    and a row step is one slot in one round."""
 
-    def __init__(self, sequences, token_logprobs, scheduler):
+    def __init__(self, sequences, token_logprobs, scheduler, num_accepted=None):
         self.sequences, self.token_logprobs = sequences, token_logprobs
         for k in ("num_decode_steps", "num_decode_forwards", "num_admissions", "num_prefills", "live_row_steps", "total_row_steps",
                   "live_fraction"):
             setattr(self, k, getattr(scheduler, k))
+        if isinstance(scheduler, LookupSlotScheduler):
+            self.num_rounds, self.num_target_forwards = scheduler.num_rounds, scheduler.num_target_forwards
+            self.num_accepted = list(num_accepted) if num_accepted is not None else [0] * len(scheduler.budget)
 
 
 def static_batch_steps(max_new_tokens, max_batch_size):
@@ -571,12 +578,92 @@ class SlotScheduler:
         return ended
 
 
+class LookupSlotScheduler(SlotScheduler):
+    """`SlotScheduler` for rounds that emit a variable number of tokens per slot (generate_batch with prompt_lookup_num_tokens): the
+    same slots, queue, admission policy (all free slots are filled in request order before every round) and admission counters;
+    `advance` replaces `step`, which stays as it is.
+
+        while not sched.finished:
+            for request, slot in sched.admit(): ...
+            ended = sched.advance(emitted, ended_slots)      # emitted: {slot: tokens its request emitted in this round}
+
+    Counters of its own: num_rounds, num_target_forwards (one verification pass per round), tokens_emitted.  A round adds
+    max_batch_size to total_row_steps and the occupied slots to live_row_steps; num_decode_steps / num_decode_forwards stay 0."""
+
+    def __init__(self, max_new_tokens, max_batch_size):
+        super().__init__(max_new_tokens, max_batch_size)
+        self.num_rounds = self.num_target_forwards = self.tokens_emitted = 0
+
+    def advance(self, emitted, ended=()):
+        """One round.  emitted: {slot: n} for every occupied slot, n >= 1 tokens (the first token of a freshly admitted slot
+        included) and never past the request's budget; ended: the slots the device reported as finished (EOS, a stop sequence, the
+        budget).  A slot in `ended` or at its budget is freed.  Returns the [(request, slot)] freed."""
+        live = self.live
+        if not live:
+            raise RuntimeError("advance() without a live slot: call admit() first")
+        emitted = {int(s): int(n) for s, n in dict(emitted).items()}
+        ended = set(int(s) for s in ended)
+        if set(emitted) != set(live):
+            raise ValueError(f"emitted names slots {sorted(emitted)}, occupied are {sorted(live)}")
+        if not ended <= set(live):
+            raise ValueError(f"slots {sorted(ended - set(live))} reported as ended hold no request")
+        for s, n in emitted.items():
+            if n < 1 or self.n_gen[s] + n > self.budget[live[s]]:
+                raise ValueError(f"slot {s}: {n} tokens emitted with {self.n_gen[s]} of {self.budget[live[s]]} already out")
+        self.num_rounds += 1
+        self.num_target_forwards += 1
+        self.total_row_steps += self.B
+        self.live_row_steps += len(live)
+        freed = []
+        for s, r in live.items():
+            self.n_gen[s] += emitted[s]
+            self.tokens_emitted += emitted[s]
+            if s in ended or self.n_gen[s] >= self.budget[r]:
+                freed.append((r, s))
+                self.slot_request[s] = None
+        return freed
+
+
+def check_batch_lookup_args(requests, prompt_lookup_num_tokens, max_matching_ngram_size, t_max, ngram_max, do_sample=False,
+                            **processors):
+    """The arguments of `generate_batch(prompt_lookup_num_tokens=k, max_matching_ngram_size=n)` beyond `check_batch_args`: greedy only,
+    unprocessed logits (the round verifies them, as `generate()`'s lookup loop does), no per-request `params`, k in 1..t_max-1 (the
+    verification chunk holds k + 1 tokens), n in 1..ngram_max and GIVEN: n None raises, so a call with prompt_lookup_num_tokens alone
+    keeps the refusal it always got (tests/test_prompt_lookup_gpu.py pins it).  `processors`: repetition_penalty, no_repeat_ngram_size, bad_words_ids,
+    suppress_tokens, min_new_tokens as name=value; one that is not at its default raises.  Stop sequences, eos / pad, per-request
+    max_new_tokens and images are supported and not checked here.  ValueError naming the argument, before any device work."""
+    if do_sample:
+        raise ValueError("do_sample=True cannot be combined with prompt_lookup_num_tokens in generate_batch: its rounds are greedy")
+    defaults = {"repetition_penalty": 1.0, "no_repeat_ngram_size": 0, "min_new_tokens": 0}
+    unknown = set(processors) - {"repetition_penalty", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "min_new_tokens"}
+    if unknown:
+        raise TypeError(f"check_batch_lookup_args: unexpected arguments {sorted(unknown)}")
+    used = [n for n, v in processors.items() if v is not None and v != defaults.get(n)]
+    if used:
+        raise ValueError(f"{', '.join(used)} cannot be combined with prompt_lookup_num_tokens: prompt-lookup decoding verifies "
+                         "unprocessed logits")
+    for i, rq in enumerate(requests):
+        if isinstance(rq, dict) and rq.get("params") is not None:
+            raise ValueError(f"request {i}: params cannot be combined with prompt_lookup_num_tokens (per-request parameters are not "
+                             "built for the lookup rounds)")
+    k, n = prompt_lookup_num_tokens, max_matching_ngram_size
+    if n is None:
+        raise ValueError("generate_batch runs prompt_lookup_num_tokens only together with an explicit max_matching_ngram_size "
+                         f"(1..{ngram_max}; HF's default is 2): prompt_lookup_num_tokens alone is refused as it was before the "
+                         "lookup rounds existed")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= t_max - 1:
+        raise ValueError(f"prompt_lookup_num_tokens must be an int in 1..{t_max - 1}, got {k!r}")
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= ngram_max:
+        raise ValueError(f"max_matching_ngram_size must be an int in 1..{ngram_max}, got {n!r}")
+
+
 def check_batch_args(requests, max_batch_size=8, max_new_tokens=16, num_beams=1, assistant_model=None, num_return_sequences=1,
                      past_key_values=None, prompt_lookup_num_tokens=None):
     """The arguments of `generate_batch` that `generate()` does not have, and the modes it leaves out.  Returns each request's
     max_new_tokens (a list).  ValueError: num_beams > 1, assistant_model, prompt_lookup_num_tokens, num_return_sequences > 1,
     past_key_values (out of scope of continuous batching), a bad max_batch_size, a request without `input_ids` or with a budget < 1, a request key other than
-    `input_ids`, `images`, `max_new_tokens` and `params` (a `RequestParams`)."""
+    `input_ids`, `images`, `max_new_tokens` and `params` (a `RequestParams`).  prompt_lookup_num_tokens is refused HERE whatever its
+    value: `generate_batch` validates the lookup pair itself (`check_batch_lookup_args`) and calls this function without it."""
     if num_beams != 1:
         raise ValueError("generate_batch does not support num_beams > 1: beam search needs its beams in adjacent rows")
     if assistant_model is not None:

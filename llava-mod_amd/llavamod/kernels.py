@@ -782,6 +782,50 @@ def slot_admit_(dst_row, prompt_ids, n_prompt_new, lens_new, req_new, hist, n_pr
          ptr(done), ptr(cache_lens), ptr(req_id))
 
 
+def _batch_lookup_state(done, hist, n_hist, n_prompt, n_gen, budget):
+    B = hist.shape[0]
+    for t in (done, hist, n_hist, n_prompt, n_gen, budget):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert hist.dim() == 2 and all(t.numel() == B for t in (done, n_hist, n_prompt, n_gen, budget))
+    return B
+
+
+def batch_lookup_first_(tokens, done, hist, n_hist, n_prompt, n_gen, budget, eos, stop=None, out=None):
+    """The first token of the freshly admitted slots of `generate_batch(prompt_lookup_num_tokens=k)` (lmod_batch_lookup_first in
+    include/lmod_hip.h), the slot state updated in place: a slot with done == 0 and n_gen == 0 appends tokens[s] (the argmax of its
+    logits row) to its history as the pending token, n_gen = 1, and is done when the token is eos, completes a stop sequence (`stop`:
+    a `seq_table` or None) or budget[s] is 1.  Returns first_tok [B] int32: that token, -1 for every other slot (`out` to reuse)."""
+    B = _batch_lookup_state(done, hist, n_hist, n_prompt, n_gen, budget)
+    first = torch.empty(B, device=hist.device, dtype=torch.int32) if out is None else out
+    for t in (tokens, first):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == B
+    sf, so, ns = stop if stop is not None else (None, None, 0)
+    call("lmod_batch_lookup_first", ptr(tokens), ptr(done), ptr(hist), hist.shape[1], ptr(n_hist), ptr(n_prompt), ptr(n_gen),
+         ptr(budget), -1 if eos is None else int(eos), ptr(sf), ptr(so), ns, ptr(first), B)
+    return first
+
+
+def batch_lookup_round_(draft, target, first_tok, done, hist, n_hist, n_prompt, n_gen, budget, cache_lens, eos, pad, stop=None,
+                        out=None):
+    """One round's acceptance, emission and end conditions for every slot (lmod_batch_lookup_round), the slot state and cache_lens
+    updated in place.  draft [B, k] (`ngram_draft`'s), target [B, k+1] (argmax of the verification rows), first_tok [B]
+    (`batch_lookup_first_`'s), cache_lens [B] as the verification pass left them.  Returns block [B, k+6] int32: columns 0..k the
+    emitted tokens then pad, k+1 n_acc, k+2 n_emit, k+3 the next pending token, k+4 fin, k+5 first_tok (`out` to reuse).  k outside
+    1..APPEND_T_MAX-1 raises (LMOD_EINVAL)."""
+    B = _batch_lookup_state(done, hist, n_hist, n_prompt, n_gen, budget)
+    k = int(draft.shape[1])
+    block = torch.empty((B, k + 6), device=hist.device, dtype=torch.int32) if out is None else out
+    for t in (draft, target, first_tok, cache_lens, block):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert tuple(draft.shape) == (B, k) and target.numel() == B * (k + 1) and tuple(block.shape) == (B, k + 6)
+    assert first_tok.numel() == B and cache_lens.numel() == B
+    sf, so, ns = stop if stop is not None else (None, None, 0)
+    call("lmod_batch_lookup_round", ptr(draft), ptr(target), ptr(first_tok), k, ptr(done), ptr(hist), hist.shape[1], ptr(n_hist),
+         ptr(n_prompt), ptr(n_gen), ptr(budget), ptr(cache_lens), -1 if eos is None else int(eos), 0 if pad is None else int(pad),
+         ptr(sf), ptr(so), ns, ptr(block), B)
+    return block
+
+
 def request_uniform(seed, req_id, n_gen, out=None):
     """u [B] fp32 in [0, 1): Philox4x32-10 at counter (req_id[s], n_gen[s], 0, 0) under the 64-bit key `seed` — one uniform per
     slot that depends on the request and its token index only (lmod_request_uniform)."""

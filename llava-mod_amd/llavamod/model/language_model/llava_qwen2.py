@@ -602,7 +602,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                        temperature=1.0, top_k=None, top_p=None, seed=None, num_beams=1, num_return_sequences=1,
                        return_dict_in_generate=False, past_key_values=None, assistant_model=None, repetition_penalty=1.0,
                        no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0, stop_sequences=None,
-                       stopping_criteria=None, prompt_lookup_num_tokens=None):
+                       stopping_criteria=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None):
         """Greedy / sampling generation over a LIST of requests with continuous batching: `max_batch_size` slots decode together and
         a slot whose request has ended (EOS, a stop sequence, its max_new_tokens) is refilled with the next request's freshly
         prefilled prompt before the next step, while the other slots keep decoding — `generate()` over a batch runs every row until
@@ -612,8 +612,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         optional `max_new_tokens` (default: the call's).  The greedy and sampling arguments of `generate()` apply to the whole call,
         with the same checks and semantics (eos_token_id, pad_token_id, do_sample / temperature / top_k / top_p / seed,
         stop_sequences / stopping_criteria, repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens,
-        min_new_tokens); num_beams > 1, assistant_model, prompt_lookup_num_tokens, num_return_sequences > 1 and past_key_values raise
-        ValueError.  Returns a
+        min_new_tokens); num_beams > 1, assistant_model, num_return_sequences > 1 and past_key_values raise ValueError.  Returns a
         list, in request order, of 1-D int64 tensors: each request's new tokens, cut after its EOS / stop sequence, no padding; with
         return_dict_in_generate a `BatchOutput` (sequences, token_logprobs when sampling, the scheduler's counters).
 
@@ -643,10 +642,30 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         bad_words_ids, suppress_tokens, eos_token_id and pad_token_id stay per call.  Such a call runs `_generate_batch_rows`: the
         same loop on the per-row kernels, with a fixed launch count per step whatever the mix, and token_logprobs for every request
         (a greedy token: log-softmax of the processed logits).  A call in which no request has `params` runs the loop below with
-        the kernels it always ran."""
+        the kernels it always ran.
+
+        prompt_lookup_num_tokens = k (1..APPEND_T_MAX-1) TOGETHER WITH max_matching_ngram_size = n (1..kernels.NGRAM_MAX; there is no
+        default here: prompt_lookup_num_tokens alone raises ValueError, as it did before these rounds existed): the same list of requests
+        in ROUNDS of prompt-lookup decoding, `_generate_batch_lookup` - every round drafts up to k tokens per slot from the slot's
+        own history, verifies all slots in one forward_append and emits 1..k+1 tokens per live slot; every request's tokens are
+        plain greedy's on that request alone, away from argmax ties.  Greedy only: do_sample, any logits processor and any request
+        with `params` raise ValueError; eos / pad, stop_sequences / stopping_criteria, per-request max_new_tokens and images work as
+        above.  The BatchOutput then also carries num_rounds, num_target_forwards and num_accepted; token_logprobs is None."""
         from ...constants import IMAGE_TOKEN_INDEX
         from ...generation import (BatchOutput, SlotScheduler, check_batch_args, check_logits_args, check_request_params,
                                    check_sample_args)
+        if prompt_lookup_num_tokens is not None:
+            from ...generation import check_batch_lookup_args
+            budgets = check_batch_args(requests, max_batch_size, max_new_tokens, num_beams, assistant_model, num_return_sequences,
+                                       past_key_values)
+            check_batch_lookup_args(requests, prompt_lookup_num_tokens, max_matching_ngram_size, K.APPEND_T_MAX, K.NGRAM_MAX, do_sample,
+                                    repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                    bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens, min_new_tokens=min_new_tokens)
+            lplan = check_logits_args(stop_sequences=stop_sequences, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
+                                      vocab_size=self.lm_head.weight.shape[0])
+            return self._generate_batch_lookup(requests, budgets, max_batch_size, eos_token_id, pad_token_id,
+                                               lplan.stops if lplan is not None else [], prompt_lookup_num_tokens,
+                                               max_matching_ngram_size, return_dict_in_generate)
         budgets = check_batch_args(requests, max_batch_size, max_new_tokens, num_beams, assistant_model, num_return_sequences,
                                    past_key_values, prompt_lookup_num_tokens)
         check_sample_args(do_sample, temperature, top_k, top_p, 1)
@@ -825,9 +844,110 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         flat = torch.stack([v for o in lps for v in o]) if sum(n_out) else torch.zeros(0, dtype=torch.int32)
         return BatchOutput(seqs, list(flat.view(torch.float32).to(dev).split(n_out)), sched)
 
-    def _admit(self, requests, budgets, group, st):
+    @torch.no_grad()
+    def _generate_batch_lookup(self, requests, budgets, max_batch_size, eos_token_id, pad_token_id, stops, k, max_ngram,
+                               return_dict_in_generate):
+        """generate_batch in rounds of prompt-lookup decoding (`generate(prompt_lookup_num_tokens=k)`'s drafter and verification pass
+        under generate_batch's scheduler, admission and slot state).  The state is generate_batch's plus `budget` [B] int32 (each
+        slot's request's max_new_tokens; admission fills it with one indexed copy), and the slot cache holds k + 1 positions more:
+        a verification pass appends k + 1 positions to every row, live or not.  Per iteration, always the same launches whatever
+        sits in the slots (generation.LookupSlotScheduler decides who sits where; all free slots are filled in request order first):
+          admit   as generate_batch (`_admit`), then the budget copy;
+          first   lmod_row_argmax_bf16 over the slots' logits rows, lmod_batch_lookup_first: a freshly admitted slot's first token
+                  becomes its pending token (and may already end it: EOS, a one-token stop sequence, a budget of 1);
+          draft   lmod_ngram_draft (draft and verification chunk; a done slot drafts nothing);
+          verify  the chunk's embeddings, ONE forward_append with T = k + 1 for every slot, the head, lmod_row_argmax_bf16;
+          round   lmod_batch_lookup_round: acceptance, emission into the history, EOS / stop sequence / budget possibly in the middle
+                  of an accepted run, the cache length (a live slot: the prompt and every emitted token but the last; an idle slot:
+                  where it was);
+          read    the round's ONE read-back, the [B, k+6] block.
+        The host never asks whether a draft exists, copies no done flag and no cache length to the device; it appends each live
+        request's first token and emitted tokens, frees the slots the block reports as finished and admits again.  Its upper bound
+        of the cache lengths (forward_append's max_len) is exact: the admitted lens plus every round's n_emit.  The logits buffer is
+        read only in the iteration after an admission, by the freshly admitted slots.  A MoE model routes the B * (k+1) rows of a
+        round - idle slots' rows included - with the eval capacity rule over the rows of that call, as `generate()`'s lookup loop
+        does over its B * (k+1).  `assisted_force_accept` (measurement only, as in `_prompt_lookup_generate`) counts every drafted
+        token as accepted."""
+        from ...constants import IMAGE_TOKEN_INDEX
+        from ...generation import BatchOutput, LookupSlotScheduler
+        sched = LookupSlotScheduler(budgets, max_batch_size)
+        if not requests:
+            return BatchOutput([], None, sched, []) if return_dict_in_generate else []
+        V = self.lm_head.weight.shape[0]
+        B, dev, cfg = max_batch_size, self.model.embed_tokens.weight.device, self.config
+        tower = self.get_image_tower()
+        extra = tower.num_patches - 1 if tower is not None else 0
+        n_ids = [int(rq["input_ids"].numel()) for rq in requests]
+        spliced = [n + (int((rq["input_ids"] == IMAGE_TOKEN_INDEX).sum()) * extra if rq.get("images") is not None else 0)
+                   for n, rq in zip(n_ids, requests)]
+        i32 = dict(device=dev, dtype=torch.int32)
+        st = SimpleNamespace(
+            cache=KVCache(cfg.num_hidden_layers, B, max(s + m for s, m in zip(spliced, budgets)) + k + 1,
+                          cfg.num_key_value_heads * cfg.head_dim, dev),
+            hist=torch.zeros((B, -(-max(n + m for n, m in zip(n_ids, budgets)) // 4) * 4), **i32),
+            n_prompt=torch.zeros(B, **i32), n_hist=torch.zeros(B, **i32), n_gen=torch.zeros(B, **i32),
+            done=torch.ones(B, **i32), req_id=torch.full((B,), -1, **i32), budget=torch.ones(B, **i32),
+            logits=torch.zeros((B, V), device=dev, dtype=BF16))
+        st.tab = K.ptr_table(st.cache.tensors())
+        stop = K.seq_table(stops, dev)
+        pad = eos_token_id if pad_token_id is None else pad_token_id
+        emb_w = self.model.embed_tokens.weight
+        bufs = (torch.empty((B, k), **i32), torch.empty((B, k + 1), **i32), torch.empty(B, **i32))
+        first, block = torch.empty(B, **i32), torch.empty((B, k + 6), **i32)
+        force = getattr(self, "assisted_force_accept", False)
+        lens_h = [0] * B                                         # the host's copy of the slot cache's lens: exact, never read back
+        out, accepted = [[] for _ in requests], [0] * len(requests)
+        was_training = self.training
+        self.eval()
+        try:
+            while not sched.finished:
+                admitted = sched.admit()
+                for with_images in (False, True):
+                    group = [(r, s) for r, s in admitted if (requests[r].get("images") is not None) == with_images]
+                    if group:
+                        for s, n in self._admit(requests, budgets, group, st, reserve=k + 1).items():
+                            lens_h[s] = n
+                if admitted:
+                    meta = torch.tensor([[s for _, s in admitted], [budgets[r] for r, _ in admitted]], dtype=torch.int32).to(dev)
+                    st.budget[meta[0]] = meta[1]                 # int32 indices: no cast launch
+                K.batch_lookup_first_(K.row_argmax(st.logits), st.done, st.hist, st.n_hist, st.n_prompt, st.n_gen, st.budget,
+                                      eos_token_id, stop, out=first)
+                draft_t, chunk, _ = K.ngram_draft(st.hist, st.n_hist, st.done, k, max_ngram, V, out=bufs)
+                if max(lens_h) + k + 1 > st.cache.smax:          # cannot happen with the reservation above; never let the pass regrow
+                    st.cache.grow(max(lens_h) + k + 1)
+                    st.tab = K.ptr_table(st.cache.tensors())
+                hid = self.model.forward_append(K.gather_rows(emb_w, None, chunk.view(-1), emb_w.shape[1]), st.cache, k + 1,
+                                                max_len=max(lens_h))
+                target = K.row_argmax(ops.linear_fwd(hid, self.head())).view(B, k + 1)
+                if force:                                        # measurement only; the -1 fill stays a mismatch
+                    target[:, :k] = torch.where(draft_t >= 0, draft_t, target[:, :k])
+                K.batch_lookup_round_(draft_t, target, first, st.done, st.hist, st.n_hist, st.n_prompt, st.n_gen, st.budget,
+                                      st.cache.lens, eos_token_id, pad, stop, out=block)
+                blk = block.cpu().tolist()                       # the round's one read-back
+                emitted, ended = {}, []
+                for s, r in sched.live.items():
+                    row = blk[s]
+                    ft, n_acc, ne = row[k + 5], row[k + 1], row[k + 2]
+                    if ft >= 0:
+                        out[r].append(ft)
+                    out[r].extend(row[:ne])
+                    accepted[r] += min(n_acc, ne)
+                    emitted[s] = int(ft >= 0) + ne
+                    lens_h[s] += ne
+                    if row[k + 4]:
+                        ended.append(s)
+                sched.advance(emitted, ended)
+        finally:
+            self.train(was_training)
+        n_out = [len(o) for o in out]
+        seqs = list(torch.tensor([t for o in out for t in o], dtype=torch.int64).to(dev).split(n_out))
+        return BatchOutput(seqs, None, sched, accepted) if return_dict_in_generate else seqs
+
+    def _admit(self, requests, budgets, group, st, reserve=0):
         """Admission of generate_batch: prefill the requests of `group` ([(request, slot)]) together and move them into their slots
-        of the state `st` (the slot cache, the generation state, the logits buffer)."""
+        of the state `st` (the slot cache, the generation state, the logits buffer).  reserve: cache positions a request needs beyond
+        prompt + budget (the lookup rounds' k + 1).  Returns {slot: the admitted cache length}: the host's bound needs no read-back
+        of its own."""
         dev = st.logits.device
         rs, slots = [r for r, _ in group], [s for _, s in group]
         ids_list = [requests[r]["input_ids"].reshape(-1).to(torch.int64).cpu() for r in rs]
@@ -842,7 +962,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
             images = torch.cat([im if im.dim() == 4 else im[None] for im in (requests[r]["images"] for r in rs)])
         tcache, lg = self._start(ids, mask, images, 0, None)
         lens_h = tcache.lens.cpu().tolist()
-        need = max(l + budgets[r] for l, r in zip(lens_h, rs))
+        need = max(l + budgets[r] for l, r in zip(lens_h, rs)) + reserve
         if need > st.cache.smax:                                 # the splice made a prompt longer than predicted
             st.cache.grow(need)
             st.tab = K.ptr_table(st.cache.tensors())
@@ -854,6 +974,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         K.slot_admit_(slots, prompt.to(dev), meta[0].contiguous(), tcache.lens, meta[1].contiguous(), st.hist, st.n_prompt, st.n_hist,
                       st.n_gen, st.done, st.cache.lens, st.req_id)
         st.logits[torch.tensor(slots, device=dev)] = lg
+        return dict(zip(slots, lens_h))
 
     @torch.no_grad()
     def _assisted_generate(self, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, draft, k,

@@ -64,6 +64,14 @@ accepted; its tokens are not greedy's).  Every round is split into draft / verif
 (model.assisted_trace).  One JSON line per B.
 
     python tools/bench_generate.py --only none --lookup 4 > profiles/prompt_lookup.jsonl
+
+--batched N --lookup k times generate_batch(prompt_lookup_num_tokens=k) (prompt-lookup decoding under continuous batching) against
+plain greedy generate_batch on the --batched request list at --max-batch-size slots, three arms alternating call by call in one
+process, one warm-up each, best of --reps with every repetition kept: greedy, lookup (random weights: what the history happens to
+offer is all that is accepted) and lookup_forced (model.assisted_force_accept).  Per arm: wall ms, ms per emitted token, rounds (or
+decode steps), prefill passes, accepted drafts and the spread between repetitions.  One JSON line.
+
+    python tools/bench_generate.py --only none --batched 24 --lookup 4 --max-batch-size 8 >> profiles/batched_lookup.jsonl
 """
 import argparse
 import json
@@ -475,6 +483,52 @@ def batched_arms(model, n_req, B, text_len, reps, n1, n2, seed=0):
         "predicted_ms_batched": round(predicted, 1), "measured_over_predicted": round(best["batched"] / predicted, 3)}), flush=True)
 
 
+def batched_lookup_arms(model, n_req, B, k, text_len, reps, seed=0, max_ngram=2):
+    """Wall ms of serving the --batched request list: plain greedy generate_batch against generate_batch(prompt_lookup_num_tokens=k),
+    as is and with every drafted token counted as accepted."""
+    import random
+    rng = random.Random(seed)
+    lengths = [rng.choice((1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64)) for _ in range(n_req)]     # batched_arms' list
+    pr = prompts(n_req, text_len, seed)
+    reqs = [dict(input_ids=pr["input_ids"][i], images=pr["images"][i:i + 1], max_new_tokens=lengths[i]) for i in range(n_req)]
+
+    def run(arm):
+        kw = {} if arm == "greedy" else dict(prompt_lookup_num_tokens=k, max_matching_ngram_size=max_ngram)
+        model.assisted_force_accept = arm == "lookup_forced"
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = model.generate_batch(reqs, max_batch_size=B, return_dict_in_generate=True, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        del model.assisted_force_accept
+        assert [len(x) for x in out.sequences] == lengths, (arm, [len(x) for x in out.sequences], lengths)
+        return e0.elapsed_time(e1), out
+
+    arms, t, outs = ("greedy", "lookup", "lookup_forced"), {}, {}
+    for rep in range(reps + 1):                                    # rep 0 warms every arm
+        for a in arms:
+            ms, outs[a] = run(a)
+            if rep:
+                t.setdefault(a, []).append(ms)
+    # random weights leave near-ties, where the chunk path and the decode path may pick different tokens: reported, not asserted
+    same = sum(bool(torch.equal(x, y)) for x, y in zip(outs["greedy"].sequences, outs["lookup"].sequences))
+    n_tok = sum(lengths)
+    rec = {"metric": "generate_batched_lookup_wall_ms", "requests": n_req, "max_batch_size": B, "k": k, "max_ngram": max_ngram,
+           "lengths": lengths, "prompt_positions": text_len - 1 + 576, "new_tokens": n_tok, "requests_equal_to_greedy": same}
+    for a in arms:
+        o, best = outs[a], min(t[a])
+        passes = o.num_decode_steps if a == "greedy" else o.num_rounds
+        rec[a] = {"ms": round(best, 1), "ms_all": [round(x, 1) for x in t[a]], "spread": round(max(t[a]) / best - 1, 4),
+                  "ms_per_token": round(best / n_tok, 3), "passes": passes, "ms_per_pass_incl_prefill": round(best / passes, 3),
+                  "num_prefills": o.num_prefills, "live_fraction": round(o.live_fraction, 4)}
+        if a != "greedy":
+            rec[a]["accepted"] = sum(o.num_accepted)
+            rec[a]["tokens_per_live_row_round"] = round(n_tok / o.live_row_steps, 3)
+    rec["lookup_over_greedy"] = round(rec["lookup"]["ms"] / rec["greedy"]["ms"], 3)
+    rec["forced_over_greedy"] = round(rec["lookup_forced"]["ms"] / rec["greedy"]["ms"], 3)
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--text-len", type=int, default=125, help="text tokens incl. the image placeholder (+575 -> prompt length)")
@@ -495,7 +549,7 @@ def main():
     ap.add_argument("--batched", type=int, default=None, help="N requests: generate_batch against static batches and a B = 1 loop")
     ap.add_argument("--max-batch-size", type=int, default=8, help="slots of the --batched arms")
     ap.add_argument("--speculative", type=int, default=None, help="k: speculative sampling (student draft / forced) against do_sample")
-    ap.add_argument("--lookup", type=int, default=None, help="k: prompt-lookup decoding (as is / acceptance forced) against greedy")
+    ap.add_argument("--lookup", type=int, default=None, help="k: prompt-lookup decoding (as is / acceptance forced) against greedy; with --batched: the generate_batch arms")
     ap.add_argument("--spec-kernel-only", type=int, default=None, help="k: lmod_spec_sample_bf16 alone, no model (for a kernel trace)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate.py measures on the GPU"
@@ -526,11 +580,13 @@ def main():
                     [int(x) for x in a.extend_only.split(",")] if a.extend_only else (1, 8), a.extend_arm_only)
     if a.assistant:
         assisted_arms(model, a.assistant, a.text_len, a.reps)
-    if a.lookup:
+    if a.lookup and a.batched:                                     # together: the lookup rounds under continuous batching
+        batched_lookup_arms(model, a.batched, a.max_batch_size, a.lookup, a.text_len, a.reps)
+    elif a.lookup:
         lookup_arms(model, a.lookup, a.text_len, a.reps)
     if a.speculative:
         speculative_arms(model, a.speculative, a.text_len, a.reps)
-    if a.batched:
+    if a.batched and not a.lookup:
         batched_arms(model, a.batched, a.max_batch_size, a.text_len, a.reps, a.n1, a.n2)
     if a.processors:
         processor_arms(model, [int(x) for x in a.processors_only.split(",")] if a.processors_only else [1, 8], a.text_len, a.reps,
