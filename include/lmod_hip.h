@@ -419,6 +419,35 @@ int lmod_gen_push_stop_rows(int* tokens, int* done, int* hist, int ld_hist, int*
                             int pad, const int* stop_flat, const int* stop_off, int n_call, int n_table, const int* stop_first,
                             const int* stop_count, int R, hipStream_t stream);
 
+/* ---- constrained decoding (generate(constraint=) / generate_batch(constraint=): a token automaton says what a row MAY emit;
+ *      csrc/constrain.hip) ------------------------------------------------------------------------------------------------------
+ * The automaton (generation.TokenConstraint), all int32: edge_off [n_states + 1], edge_tok / edge_next [E] (CSR: state s owns the
+ *   edges [edge_off[s], edge_off[s+1]), tokens strictly ascending inside a state), default_next [n_states], flags [n_states] (bit 0
+ *   accept: the row may end here, so eos is allowed; bit 1 terminal: a row that enters is finished).  State s is CLOSED when
+ *   default_next[s] < 0 - only tokens with a listed edge whose next >= 0 are allowed - and OPEN otherwise: every token is allowed,
+ *   an unlisted one leads to default_next[s], a listed edge redirects its token and one with next < 0 bans it.  state [R]: a row's
+ *   current state; a value outside [0, n_states) means "unconstrained" (-1 by convention) and is never used as an index.  The
+ *   tables are the host's (validated there); the device trusts them.  n_states >= 1; R == 0 is a no-op.
+ * lmod_constrain_mask_rows_bf16: edits logits [R, ld] bf16 (V live columns, ld >= V) in place, one workgroup of 256 threads per row,
+ *   after every other processor.  A row with state outside [0, n_states) is not touched.  Open state: every listed edge with
+ *   next < 0 and 0 <= tok < V gets bf16 -inf, and so does eos (0 <= eos < V) unless the state accepts; nothing else is read or
+ *   written.  Closed state: the allowed tokens - edges with next >= 0 and 0 <= tok < V, and eos when the state accepts - are
+ *   collected in a V-bit bitmap in LDS, then every element whose bit is clear becomes bf16 -inf (0xff80).  An allowed element
+ *   keeps its bits (NaN, -inf, -0 included).  16-byte-aligned rows are swept 8 elements at a time (a vector that is allowed as a
+ *   whole is not written, one that is banned as a whole is not read), the last V % 8 elements and unaligned rows (ld * 2 not a
+ *   multiple of 16) element by element.  V > 524288 (64 KB of LDS) has no bitmap: open states work as above, a row in a closed
+ *   state is left untouched - the caller refuses such a call beforehand (kernels.constrain_mask_ raises).  eos < 0: no such token.
+ * lmod_constrain_advance_rows: one thread per row, after lmod_gen_push_stop / lmod_gen_push_stop_rows.  A row with done[r] != 0 (finished
+ *   earlier, or by this step's EOS / stop sequence) or with state[r] outside [0, n_states) is left as it is.  Otherwise
+ *   ns = edge_next[e] when tokens[r] has an edge e in the state (binary search), else default_next[state[r]].  ns < 0 (the token
+ *   left the automaton; with the mask applied only when the row had no allowed token left): done[r] = 1, the state stays.
+ *   Otherwise state[r] = ns, and done[r] = 1 when ns is terminal: the row is finished by that token, as by a stop sequence. */
+int lmod_constrain_mask_rows_bf16(void* logits, long long ld, int V, int R, const int* state, const int* edge_off, const int* edge_tok,
+                                  const int* edge_next, const int* default_next, const int* flags, int n_states, int eos,
+                                  hipStream_t stream);
+int lmod_constrain_advance_rows(const int* tokens, int* done, int* state, const int* edge_off, const int* edge_tok, const int* edge_next,
+                                const int* default_next, const int* flags, int n_states, int R, hipStream_t stream);
+
 /* ---- continuous batching (generate_batch(): a finished slot of the running batch is refilled while the others keep decoding;
  *      csrc/batch.hip) -------------------------------------------------------------------------------------------------------
  * lmod_kv_admit_rows: the scatter that lmod_kv_gather_rows is not.  For every tensor t < ntensor (device tables dst[t] / src[t], 16-byte

@@ -171,17 +171,22 @@ class BeamSearchOutput:
 class SampleOutput:
     """`generate(do_sample=True, return_dict_in_generate=True)`: sequences int64 [B*n, L] (new tokens only, sample b's n
     continuations in rows b*n .. b*n+n-1) and token_logprobs fp32 [B*n, L]: the log-probability of each drawn token under the
-    warped (temperature / top-k / top-p) distribution it was drawn from, 0 at positions after a sequence's EOS."""
+    warped (temperature / top-k / top-p) distribution it was drawn from, 0 at positions after a sequence's EOS.  With
+    `generate(constraint=...)`: constraint_states int32 [B*n], every row's final automaton state (None otherwise), and the
+    log-probabilities are under the masked, warped distribution."""
 
-    def __init__(self, sequences, token_logprobs, past_key_values=None):
+    def __init__(self, sequences, token_logprobs, past_key_values=None, constraint_states=None):
         self.sequences, self.token_logprobs, self.past_key_values = sequences, token_logprobs, past_key_values
+        self.constraint_states = constraint_states
 
 
 class GreedyOutput:
-    """`generate(return_dict_in_generate=True)` without sampling or beams: sequences int64 [B, L] (new tokens only) and the KV cache."""
+    """`generate(return_dict_in_generate=True)` without sampling or beams: sequences int64 [B, L] (new tokens only) and the KV cache.
+    With `generate(constraint=...)`: constraint_states int32 [B], every row's final automaton state (None otherwise) - the caller
+    checks `constraint.accept[state]` on it, for example when max_new_tokens cut an answer short."""
 
-    def __init__(self, sequences, past_key_values=None):
-        self.sequences, self.past_key_values = sequences, past_key_values
+    def __init__(self, sequences, past_key_values=None, constraint_states=None):
+        self.sequences, self.past_key_values, self.constraint_states = sequences, past_key_values, constraint_states
 
 
 # ---------------------------------------------------------------------------------------------- assisted (speculative) decoding
@@ -704,19 +709,22 @@ class RequestParams:
     the call's argument of the same name.  stop_sequences apply IN ADDITION to the call's.  seed: the request's k-th uniform is
     Philox4x32-10 with key = seed at counter (0, k, 0, 0) — the same draws wherever the request stands in the list and whichever call
     carries it; without one it keeps the call's stream, key = the call's seed at counter (request index, k, 0, 0).  bad_words_ids,
-    suppress_tokens, eos_token_id and pad_token_id stay per call."""
+    suppress_tokens, eos_token_id and pad_token_id stay per call.  constraint: the request's own `TokenConstraint` instead of the
+    call's (None inherits the call's; `NO_CONSTRAINT` turns the call's off for this request); it is not one of FIELDS: the slot's
+    automaton state is an array of its own, not a column of the parameter table."""
 
     FIELDS = ("do_sample", "temperature", "top_k", "top_p", "seed", "repetition_penalty", "no_repeat_ngram_size", "min_new_tokens",
               "stop_sequences")
 
     def __init__(self, do_sample=None, temperature=None, top_k=None, top_p=None, seed=None, repetition_penalty=None,
-                 no_repeat_ngram_size=None, min_new_tokens=None, stop_sequences=None):
+                 no_repeat_ngram_size=None, min_new_tokens=None, stop_sequences=None, constraint=None):
         self.do_sample, self.temperature, self.top_k, self.top_p, self.seed = do_sample, temperature, top_k, top_p, seed
         self.repetition_penalty, self.no_repeat_ngram_size, self.min_new_tokens = repetition_penalty, no_repeat_ngram_size, min_new_tokens
-        self.stop_sequences = stop_sequences
+        self.stop_sequences, self.constraint = stop_sequences, constraint
 
     def __repr__(self):
-        return "RequestParams(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS if getattr(self, k) is not None) + ")"
+        return "RequestParams(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS + ("constraint",)
+                                            if getattr(self, k) is not None) + ")"
 
 
 class RequestRecord:
@@ -838,3 +846,264 @@ def check_request_params(requests, do_sample=False, temperature=1.0, top_k=None,
                        any_process=bool(bad) or any(r.penalty != 1.0 or r.ngram > 0 or r.min_new > 0 for r in records),
                        any_penalty=any(r.penalty != 1.0 for r in records),
                        needs_call_seed=any(r.do_sample and not r.own_seed for r in records))
+
+
+# ---------------------------------------------------------------------------------------------- constrained decoding
+class TokenConstraint:
+    """A deterministic finite automaton over token ids: what a row of `generate(constraint=...)` MAY emit.  States are
+    0 .. n_states-1; a row starts in `start`.  A state s is CLOSED (default_next[s] == -1: only tokens with a listed edge whose next is
+    >= 0 are allowed) or OPEN (default_next[s] = d >= 0: every token is allowed, an unlisted one leads to d, a listed edge redirects
+    its token and one with next == -1 bans it).  accept[s]: the row may end here, so EOS is allowed in this state; terminal[s]:
+    accepting, closed and without an allowed edge - a row that enters it is finished by that token.
+
+        TokenConstraint(n_states, edges, accepting, default=None, start=0)
+
+    edges: an iterable of (state, token, next or -1); accepting: an iterable of states; default: None (every state closed), one int
+    for every state, a sequence of n_states ints or a dict {state: d}.  ValueError for a duplicate (state, token), for a state, next,
+    default or start out of range, and for a dead end (a closed, non-accepting state without an allowed edge).  Token ids are
+    checked against a vocabulary by `check_constraint_args`.
+
+    The device form (lmod_constrain_mask_rows_bf16 / lmod_constrain_advance_rows), plain int lists here: edge_off [n_states + 1],
+    edge_tok / edge_next [E] (CSR, tokens strictly ascending inside a state), default_next [n_states], flags [n_states] (bit 0
+    accept, bit 1 terminal)."""
+
+    ACCEPT, TERMINAL = 1, 2
+
+    def __init__(self, n_states, edges, accepting, default=None, start=0):
+        n = n_states
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"n_states must be an int >= 1, got {n!r}")
+
+        def _int(name, v, lo):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v < n:
+                raise ValueError(f"{name} must be an int in [{lo}, {n}), got {v!r}")
+            return v
+
+        if default is None:
+            dn = [-1] * n
+        elif isinstance(default, dict):
+            dn = [-1] * n
+            for st, d in default.items():
+                dn[_int("a state of default", st, 0)] = d
+        elif isinstance(default, int):
+            dn = [default] * n
+        else:
+            dn = list(default)
+            if len(dn) != n:
+                raise ValueError(f"default lists {len(dn)} states, the automaton has {n}")
+        self.default_next = [_int("default", d, -1) for d in dn]
+        self.n_states, self.start = n, _int("start", start, 0)
+        per = [{} for _ in range(n)]
+        for e in edges:
+            st, tok, nx = e
+            _int("an edge's state", st, 0)
+            if isinstance(tok, bool) or not isinstance(tok, int):
+                raise ValueError(f"an edge's token must be an int, got {tok!r}")
+            if tok in per[st]:
+                raise ValueError(f"duplicate edge: state {st}, token {tok}")
+            per[st][tok] = _int("an edge's next state", nx, -1)
+        self.accept = [False] * n
+        for st in accepting:
+            self.accept[_int("an accepting state", st, 0)] = True
+        self.edge_off, self.edge_tok, self.edge_next = [0], [], []
+        for d in per:
+            for tok in sorted(d):
+                self.edge_tok.append(tok)
+                self.edge_next.append(d[tok])
+            self.edge_off.append(len(self.edge_tok))
+        self.terminal = []
+        for st in range(n):
+            stuck = self.default_next[st] < 0 and not any(nx >= 0 for nx in per[st].values())
+            if stuck and not self.accept[st]:
+                raise ValueError(f"state {st} is a dead end: closed, not accepting and without an allowed edge")
+            self.terminal.append(stuck)
+        self.flags = [self.ACCEPT * a + self.TERMINAL * t for a, t in zip(self.accept, self.terminal)]
+
+    @property
+    def has_closed(self):
+        """Some state is closed: lmod_constrain_mask_rows_bf16 then needs its V-bit bitmap."""
+        return any(d < 0 for d in self.default_next)
+
+    @property
+    def has_terminal(self):
+        return any(self.terminal)
+
+    def edges(self):
+        """The edges as a list of (state, token, next), state by state, tokens ascending."""
+        return [(st, self.edge_tok[e], self.edge_next[e]) for st in range(self.n_states)
+                for e in range(self.edge_off[st], self.edge_off[st + 1])]
+
+    @classmethod
+    def from_choices(cls, seqs):
+        """Exactly one of these token sequences: a trie of closed states.  Duplicates are dropped; a choice that is a proper prefix of
+        another ends in an accepting state that is not terminal (the row may stop there or go on).  ValueError for an empty choice
+        or an empty list."""
+        seqs = [list(s.tolist() if hasattr(s, "tolist") else s) for s in seqs]
+        if not seqs:
+            raise ValueError("from_choices needs at least one choice")
+        children, accepting = [{}], set()
+        for s in seqs:
+            if not s:
+                raise ValueError("from_choices: an empty choice")
+            node = 0
+            for tok in s:
+                if isinstance(tok, bool) or not isinstance(tok, int):
+                    raise ValueError(f"from_choices: token id {tok!r} is not an int")
+                if tok not in children[node]:
+                    children[node][tok] = len(children)
+                    children.append({})
+                node = children[node][tok]
+            accepting.add(node)
+        return cls(len(children), [(st, tok, nx) for st, d in enumerate(children) for tok, nx in d.items()], sorted(accepting))
+
+    @classmethod
+    def from_allowed_tokens(cls, tokens):
+        """Only these tokens, any number of them: one closed, accepting state with a self-loop per token (the constant case of HF's
+        prefix_allowed_tokens_fn)."""
+        tokens = sorted(set(tokens.tolist() if hasattr(tokens, "tolist") else tokens))
+        if not tokens:
+            raise ValueError("from_allowed_tokens needs at least one token")
+        return cls(1, [(0, tok, 0) for tok in tokens], [0])
+
+    @classmethod
+    def merge(cls, constraints):
+        """The disjoint union of a list of constraints (None entries allowed) with state offsets, for a batch whose rows follow
+        different automata through one set of tables.  Returns (merged, starts): starts[i] is constraint i's start state inside
+        `merged`, -1 for None; merged is None when every entry is."""
+        edges, accepting, default, starts, off = [], [], [], [], 0
+        for c in constraints:
+            if c is None:
+                starts.append(-1)
+                continue
+            if not isinstance(c, cls):
+                raise ValueError(f"merge: a TokenConstraint or None is expected, got {type(c).__name__}")
+            edges += [(st + off, tok, nx + off if nx >= 0 else -1) for st, tok, nx in c.edges()]
+            accepting += [st + off for st in range(c.n_states) if c.accept[st]]
+            default += [d + off if d >= 0 else -1 for d in c.default_next]
+            starts.append(c.start + off)
+            off += c.n_states
+        return (cls(off, edges, accepting, default) if off else None), starts
+
+    def walk(self, tokens, state=None):
+        """The transition rule in plain Python - what lmod_constrain_advance_rows does with one token at a time.  From `state` (the
+        start state by default) follow `tokens`: a listed edge leads to its next state, an unlisted token to the state's default.
+        Returns (state, ok): ok False at the first token that is not allowed (next -1); the state is then the one that refused it."""
+        s = self.start if state is None else state
+        for tok in tokens:
+            lo, hi = self.edge_off[s], self.edge_off[s + 1]
+            nx = self.default_next[s]
+            for e in range(lo, hi):
+                if self.edge_tok[e] == int(tok):
+                    nx = self.edge_next[e]
+                    break
+            if nx < 0:
+                return s, False
+            s = nx
+        return s, True
+
+    def __repr__(self):
+        return f"TokenConstraint(n_states={self.n_states}, edges={len(self.edge_tok)}, start={self.start})"
+
+
+class _NoConstraint:
+    def __repr__(self):
+        return "NO_CONSTRAINT"
+
+
+NO_CONSTRAINT = _NoConstraint()           # RequestParams(constraint=NO_CONSTRAINT): this request ignores the call's constraint
+
+
+def _constraint_vocab(constraint, vocab_size, who="constraint"):
+    from .kernels import CONSTRAIN_MAX_V
+    if not isinstance(constraint, TokenConstraint):
+        raise ValueError(f"{who} must be a generation.TokenConstraint, got {type(constraint).__name__}")
+    if vocab_size is None:
+        raise ValueError("vocab_size is needed to check token ids")
+    for tok in constraint.edge_tok:
+        if not 0 <= tok < vocab_size:
+            raise ValueError(f"{who}: token id {tok} is not in [0, {vocab_size})")
+    if constraint.has_closed and vocab_size > CONSTRAIN_MAX_V:
+        raise ValueError(f"{who}: a closed state needs a {vocab_size}-bit bitmap in LDS: a vocabulary above {CONSTRAIN_MAX_V} is not "
+                         "supported")
+
+
+def _banning(no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0):
+    given = {"no_repeat_ngram_size": no_repeat_ngram_size not in (0, None), "bad_words_ids": bad_words_ids is not None,
+             "suppress_tokens": suppress_tokens is not None, "min_new_tokens": min_new_tokens not in (0, None)}
+    return [k for k, v in given.items() if v]
+
+
+_BANNING_MSG = ("{used} cannot be combined with a constraint: a banning processor can empty a row's allowed set, and combining the "
+                "two is not built yet (repetition_penalty and stop sequences are fine)")
+
+
+def check_constraint_args(constraint, vocab_size, num_beams=1, assistant_model=None, prompt_lookup_num_tokens=None,
+                          speculative_sampling=False, no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None,
+                          min_new_tokens=0):
+    """`generate(constraint=...)` beside its other arguments; nothing to check without a constraint.  ValueError, before anything is
+    launched: a token id outside [0, vocab_size); num_beams > 1, assistant_model, prompt_lookup_num_tokens or speculative_sampling
+    (those loops verify or score logits the mask does not reach); a banning processor (no_repeat_ngram_size, bad_words_ids,
+    suppress_tokens, min_new_tokens: it can empty a row's allowed set - not built yet); a closed state with a vocabulary above
+    kernels.CONSTRAIN_MAX_V.  repetition_penalty, stop_sequences and stopping_criteria combine freely."""
+    if constraint is None:
+        return
+    _constraint_vocab(constraint, vocab_size)
+    modes = {"num_beams > 1": num_beams != 1, "assistant_model": assistant_model is not None,
+             "prompt_lookup_num_tokens": prompt_lookup_num_tokens is not None, "speculative_sampling": bool(speculative_sampling)}
+    used = [k for k, v in modes.items() if v]
+    if used:
+        raise ValueError(f"constraint cannot be combined with {', '.join(used)}: that loop verifies or scores logits the "
+                         "constraint's mask does not reach")
+    used = _banning(no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens)
+    if used:
+        raise ValueError(_BANNING_MSG.format(used=", ".join(used)))
+
+
+class ConstraintPlan:
+    """What `check_batch_constraint_args` made of a generate_batch call: merged (ONE TokenConstraint: the disjoint union of the
+    call's distinct constraints) and starts (per request: its start state inside `merged`, -1 for an unconstrained request)."""
+
+    def __init__(self, merged, starts):
+        self.merged, self.starts = merged, starts
+
+
+def check_batch_constraint_args(requests, constraint, vocab_size, prompt_lookup_num_tokens=None, no_repeat_ngram_size=0,
+                                bad_words_ids=None, suppress_tokens=None, min_new_tokens=0):
+    """`generate_batch(constraint=...)` and every request's `params.constraint`: a request's own constraint overrides the call's,
+    None inherits it, NO_CONSTRAINT turns it off.  Returns None when no request ends up constrained and the call gives none (the
+    caller then allocates and launches nothing new), else a `ConstraintPlan`.  ValueError, naming the request, before any device
+    work: the token and vocabulary rules of `check_constraint_args`; prompt_lookup_num_tokens; a banning processor (the request's
+    effective no_repeat_ngram_size / min_new_tokens, the call's bad_words_ids / suppress_tokens) on a CONSTRAINED request -
+    unconstrained requests of the same list may use them."""
+    eff = []
+    for i, rq in enumerate(requests):
+        prm = rq.get("params") if isinstance(rq, dict) else None
+        own = getattr(prm, "constraint", None)
+        c = constraint if own is None else (None if own is NO_CONSTRAINT else own)
+        eff.append(c)
+    if constraint is None and all(c is None for c in eff):
+        return None
+    if constraint is not None:
+        _constraint_vocab(constraint, vocab_size)
+    if prompt_lookup_num_tokens is not None:
+        raise ValueError("constraint cannot be combined with prompt_lookup_num_tokens: the lookup rounds verify logits the "
+                         "constraint's mask does not reach")
+    for i, (rq, c) in enumerate(zip(requests, eff)):
+        if c is None:
+            continue
+        _constraint_vocab(c, vocab_size, f"request {i}: constraint")
+        prm = rq.get("params")
+        own = lambda name, call: call if getattr(prm, name, None) is None else getattr(prm, name)
+        used = _banning(own("no_repeat_ngram_size", no_repeat_ngram_size), bad_words_ids, suppress_tokens,
+                        own("min_new_tokens", min_new_tokens))
+        if used:
+            raise ValueError(f"request {i}: " + _BANNING_MSG.format(used=", ".join(used)))
+    distinct = []
+    for c in eff:
+        if c is not None and not any(c is d for d in distinct):
+            distinct.append(c)
+    merged, first = TokenConstraint.merge(distinct)
+    if merged is None:                                     # the call's constraint is turned off by every request
+        return None
+    starts = [-1 if c is None else first[next(j for j, d in enumerate(distinct) if d is c)] for c in eff]
+    return ConstraintPlan(merged, starts)

@@ -702,6 +702,52 @@ def gen_push_stop_(tokens, done, hist, n_hist, n_prompt, n_gen, eos, pad, stop=N
          -1 if eos is None else int(eos), 0 if pad is None else int(pad), ptr(sf), ptr(so), ns, R)
 
 
+# ------------------------------------------------------------------------------------------ constrained decoding
+CONSTRAIN_MAX_V = 524288      # csrc/constrain.hip: the V-bit bitmap of a closed state, 64 KB of LDS (the penalty bitmap's limit)
+
+
+def constraint_table(c, device):
+    """A `generation.TokenConstraint` as the device tables the constrain kernels read - `seq_table`'s sibling: (edge_off [n + 1],
+    edge_tok [E], edge_next [E], default_next [n], flags [n], n, has_closed), the arrays int32 views of one buffer, n and has_closed
+    host values.  One host -> device copy."""
+    n, E = c.n_states, len(c.edge_tok)
+    both = torch.tensor(c.edge_off + c.edge_tok + c.edge_next + c.default_next + c.flags, dtype=torch.int32).to(device)
+    cut = [0, n + 1, n + 1 + E, n + 1 + 2 * E, 2 * n + 1 + 2 * E, 3 * n + 1 + 2 * E]
+    return tuple(both[a:b] for a, b in zip(cut, cut[1:])) + (n, c.has_closed)
+
+
+def _constraint_args(table, state, R):
+    off, tok, nxt, dflt, flags, n, _ = table
+    for t in (off, tok, nxt, dflt, flags, state):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert off.numel() == n + 1 and dflt.numel() == n and flags.numel() == n and tok.numel() == nxt.numel() and state.numel() == R
+    return ptr(off), ptr(tok) if tok.numel() else None, ptr(nxt) if nxt.numel() else None, ptr(dflt), ptr(flags), n
+
+
+def constrain_mask_(logits, state, table, eos=None):
+    """In place on logits [R, V] bf16 (row stride may exceed V): every row whose state [R] (device int32) is inside the automaton
+    `table` (`constraint_table`) keeps only what that state allows, everything else becomes -inf; a row with state -1 is not
+    touched (lmod_constrain_mask_rows_bf16 in include/lmod_hip.h).  Runs after every other processor.  ValueError, and no launch,
+    when the automaton has a closed state and V exceeds the LDS bitmap.  Returns logits."""
+    R, V = logits.shape
+    assert logits.dtype == BF16 and logits.is_cuda and logits.stride(1) == 1
+    args = _constraint_args(table, state, R)
+    if table[6] and V > CONSTRAIN_MAX_V:
+        raise ValueError(f"a closed constraint state needs a {V}-bit bitmap in LDS: a vocabulary above {CONSTRAIN_MAX_V} is not supported")
+    call("lmod_constrain_mask_rows_bf16", ptr(logits), logits.stride(0), V, R, ptr(state), *args, -1 if eos is None else int(eos))
+    return logits
+
+
+def constrain_advance_(tokens, done, state, table):
+    """One generation step's automaton bookkeeping on the device (lmod_constrain_advance_rows), after `gen_push_stop_`: a live row
+    in a valid state follows its token's edge; done[r] is set when the row enters a terminal state or its token left the automaton.
+    tokens / done / state: device int32 [R], done and state updated in place."""
+    R = tokens.numel()
+    for t in (tokens, done):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == R
+    call("lmod_constrain_advance_rows", ptr(tokens), ptr(done), ptr(state), *_constraint_args(table, state, R), R)
+
+
 # ------------------------------------------------------------------------------------------ prompt-lookup decoding
 NGRAM_MAX = 8              # csrc/lookup.hip: the longest trailing n-gram lmod_ngram_draft looks up
 

@@ -371,7 +371,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                  past_key_values=None, assistant_model=None, num_assistant_tokens=5, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0, stop_sequences=None,
                  stopping_criteria=None, speculative_sampling=False, prompt_lookup_num_tokens=None, max_matching_ngram_size=2,
-                 **kwargs):
+                 constraint=None, **kwargs):
         """Generation with a KV cache (the reference's eval path calls HF `generate` on the Eval model,
         llava_qwen2_moe.py:629-681; its serving code passes do_sample / temperature / top_p, its eval scripts num_beams).
         Greedy by default; do_sample=True draws from the temperature / top-k / top-p filtered distribution (`seed` makes the
@@ -428,8 +428,24 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         sequences join stop_sequences.  Only that token-level test is reproduced: the class's string-level fallback (decode, then
         substring search) and its all() over the batch are not; anything else raises TypeError.  At most kernels.LOGITS_MAX_SEQS
         sequences of at most kernels.LOGITS_MAX_SEQ_LEN tokens per table, ids in [0, V).  A call that uses none of these arguments
-        runs the loop below exactly as before."""
+        runs the loop below exactly as before.
+
+        constraint (a `generation.TokenConstraint`: a finite automaton over token ids, e.g. `from_choices` over the option letters
+        of a multiple-choice prompt or `from_allowed_tokens`): what a row MAY emit.  Every row carries one int32 state on the
+        device; per step lmod_constrain_mask_rows_bf16 sets every logit the state does not allow to -inf - after the processors
+        above, HF's position for PrefixConstrainedLogitsProcessor, so sampling draws from, and token_logprobs are under, the
+        masked distribution - and lmod_constrain_advance_rows follows the selected token's edge after lmod_gen_push_stop.  EOS
+        is allowed in accepting states only; a row that enters a terminal state is finished by that token, as by a stop sequence
+        (later positions hold pad_token_id).  Greedy and sampling, num_return_sequences, past_key_values, repetition_penalty and stop
+        sequences work with it; num_beams > 1, assistant_model, speculative_sampling, prompt_lookup_num_tokens and the banning
+        processors (no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens) raise ValueError.  With
+        return_dict_in_generate the result carries `constraint_states` (int32 [rows]: the final states).  None: nothing new is
+        allocated or launched."""
         from ...generation import check_logits_args
+        if constraint is not None:
+            from ...generation import check_constraint_args
+            check_constraint_args(constraint, self.lm_head.weight.shape[0], num_beams, assistant_model, prompt_lookup_num_tokens,
+                                  speculative_sampling, no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens)
         if prompt_lookup_num_tokens is not None:
             from ...generation import check_prompt_lookup_args
             check_prompt_lookup_args(prompt_lookup_num_tokens, max_matching_ngram_size, K.APPEND_T_MAX, K.NGRAM_MAX, do_sample, num_beams,
@@ -465,10 +481,13 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                                        past_key_values)
         from ...generation import GreedyOutput, SampleOutput, check_sample_args
         check_sample_args(do_sample, temperature, top_k, top_p, num_return_sequences)
-        if lplan is not None:
+        if lplan is not None or constraint is not None:
+            if lplan is None:
+                from ...generation import LogitsPlan
+                lplan = LogitsPlan(1.0, 0, [], 0, [])              # no processor, no stop sequence: the constraint alone
             return self._processed_generate(lplan, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id,
                                             do_sample, temperature, top_k, top_p, seed, num_return_sequences,
-                                            return_dict_in_generate, past_key_values)
+                                            return_dict_in_generate, past_key_values, constraint)
         n = num_return_sequences
         on_device = do_sample and self.sample_on_device
         was_training = self.training
@@ -524,13 +543,16 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
 
     @torch.no_grad()
     def _processed_generate(self, lplan, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, do_sample,
-                            temperature, top_k, top_p, seed, n, return_dict_in_generate, past):
+                            temperature, top_k, top_p, seed, n, return_dict_in_generate, past, constraint=None):
         """Greedy / sampling generate() with logits processors and stop sequences (`lplan`, generation.check_logits_args).  The
         token history [rows, prompt + max_new_tokens], its counters and the done flags live on the device, allocated once; per
         step: lmod_logits_process_bf16 in place on the step's logits (when a processor is active), the usual selection
         (lmod_row_argmax_bf16 / lmod_sample_bf16), lmod_gen_push_stop (pad, history append, EOS and stop-sequence test), one
         read-back of the done flags, one decode step.  `logits_glue` (measurement only, tools/bench_generate.py --processors): a
-        pair of torch functions (process, push) that stand in for the two kernels, the A/B baseline as `sample_on_device` is."""
+        pair of torch functions (process, push) that stand in for the two kernels, the A/B baseline as `sample_on_device` is.
+        constraint (a generation.TokenConstraint): its tables go to the device once, every row's state is one int32 [rows] that
+        starts at `constraint.start`; lmod_constrain_mask_rows_bf16 runs last before the selection and
+        lmod_constrain_advance_rows right after lmod_gen_push_stop - no read-back and no host -> device copy of their own."""
         from ...generation import GreedyOutput, SampleOutput
         glue = getattr(self, "logits_glue", None)
         on_device = do_sample and self.sample_on_device
@@ -545,6 +567,10 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                         else torch.full((B,), S, device=dev, dtype=torch.int32))
             hist = torch.zeros((B, S + max_new_tokens), device=dev, dtype=torch.int32)
             hist[:, :S] = ids
+            ctab = cstate = None
+            if constraint is not None:
+                ctab = K.constraint_table(constraint, dev)
+                cstate = torch.full((B,), constraint.start, device=dev, dtype=torch.int32)
             if n > 1:
                 cfg = self.config
                 pcache, cache = cache, KVCache(cfg.num_hidden_layers, B * n, cache.smax, cfg.num_key_value_heads * cfg.head_dim, dev)
@@ -552,13 +578,15 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                 K.kv_gather_rows(cache.tensors(), pcache.tensors(), torch.arange(B * n, device=dev, dtype=torch.int32) // n, cache.lens)
                 del pcache
                 logits, hist, n_prompt = logits.repeat_interleave(n, 0), hist.repeat_interleave(n, 0), n_prompt.repeat_interleave(n)
+                if cstate is not None:
+                    cstate = cstate.repeat_interleave(n).contiguous()
                 B = B * n
             hist, n_prompt = hist.contiguous(), n_prompt.contiguous()
             n_hist, n_gen = n_prompt.clone(), torch.zeros(B, device=dev, dtype=torch.int32)
             done = torch.zeros(B, device=dev, dtype=torch.int32)
             bad, stop = K.seq_table(lplan.bad, dev), K.seq_table(lplan.stops, dev)
             pad = eos_token_id if pad_token_id is None else pad_token_id
-            can_stop = eos_token_id is not None or stop is not None
+            can_stop = eos_token_id is not None or stop is not None or (constraint is not None and constraint.has_terminal)
             gen = None
             if do_sample:
                 gen = torch.Generator(device=dev)
@@ -571,6 +599,8 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                 elif lplan.process:
                     logits = glue[0](logits, hist, n_hist, n_gen, penalty=lplan.penalty, ngram=lplan.ngram, bad=lplan.bad,
                                      min_new=lplan.min_new, eos=eos_token_id)
+                if ctab is not None:
+                    K.constrain_mask_(logits, cstate, ctab, eos_token_id)
                 if on_device:
                     u = torch.rand(B, generator=gen, device=dev)
                     nxt = K.sample(logits, u, temperature, top_k, top_p, stats=want_lp)
@@ -585,6 +615,8 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                     K.gen_push_stop_(nxt, done, hist, n_hist, n_prompt, n_gen, eos_token_id, pad, stop)
                 else:
                     nxt, done, hist, n_hist, n_gen = glue[1](nxt, done, hist, n_hist, n_prompt, n_gen, eos_token_id, pad, lplan.stops)
+                if ctab is not None:
+                    K.constrain_advance_(nxt, done, cstate, ctab)
                 out.append(nxt.long())
                 if step + 1 == max_new_tokens or (can_stop and bool(done.all())):
                     break
@@ -593,8 +625,8 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
             self.train(was_training)
         seq = torch.stack(out, 1)
         if do_sample and return_dict_in_generate:
-            return SampleOutput(seq, torch.stack(lps, 1) if lps else None, cache)
-        return GreedyOutput(seq, cache) if return_dict_in_generate else seq
+            return SampleOutput(seq, torch.stack(lps, 1) if lps else None, cache, cstate)
+        return GreedyOutput(seq, cache, cstate) if return_dict_in_generate else seq
 
     # ---- continuous batching -------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -602,7 +634,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                        temperature=1.0, top_k=None, top_p=None, seed=None, num_beams=1, num_return_sequences=1,
                        return_dict_in_generate=False, past_key_values=None, assistant_model=None, repetition_penalty=1.0,
                        no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0, stop_sequences=None,
-                       stopping_criteria=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None):
+                       stopping_criteria=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, constraint=None):
         """Greedy / sampling generation over a LIST of requests with continuous batching: `max_batch_size` slots decode together and
         a slot whose request has ended (EOS, a stop sequence, its max_new_tokens) is refilled with the next request's freshly
         prefilled prompt before the next step, while the other slots keep decoding — `generate()` over a batch runs every row until
@@ -650,10 +682,20 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         own history, verifies all slots in one forward_append and emits 1..k+1 tokens per live slot; every request's tokens are
         plain greedy's on that request alone, away from argmax ties.  Greedy only: do_sample, any logits processor and any request
         with `params` raise ValueError; eos / pad, stop_sequences / stopping_criteria, per-request max_new_tokens and images work as
-        above.  The BatchOutput then also carries num_rounds, num_target_forwards and num_accepted; token_logprobs is None."""
+        above.  The BatchOutput then also carries num_rounds, num_target_forwards and num_accepted; token_logprobs is None.
+
+        constraint (a `generation.TokenConstraint`, as in `generate()`): what every request may emit; a request's own
+        `params.constraint` overrides it (None inherits, generation.NO_CONSTRAINT turns it off for that request).  The distinct
+        constraints of the call are merged once into one set of tables (`TokenConstraint.merge`); the slot state gains `cstate`
+        [max_batch_size] int32 (-1: the slot's request is unconstrained, or the slot was never admitted), written with the
+        admitted slots' start states by one indexed copy after an admission.  When the call has any constraint, every step makes the
+        same two launches in both loops - lmod_constrain_mask_rows_bf16 before the selection, lmod_constrain_advance_rows after
+        the push - whichever requests sit in the slots; without one nothing new is allocated or launched.  A slot finished by a
+        terminal state is refilled on the next iteration like one finished by EOS.  With prompt_lookup_num_tokens, or with a banning
+        processor in force on a constrained request, it raises ValueError."""
         from ...constants import IMAGE_TOKEN_INDEX
-        from ...generation import (BatchOutput, SlotScheduler, check_batch_args, check_logits_args, check_request_params,
-                                   check_sample_args)
+        from ...generation import (BatchOutput, SlotScheduler, check_batch_args, check_batch_constraint_args, check_logits_args,
+                                   check_request_params, check_sample_args)
         if prompt_lookup_num_tokens is not None:
             from ...generation import check_batch_lookup_args
             budgets = check_batch_args(requests, max_batch_size, max_new_tokens, num_beams, assistant_model, num_return_sequences,
@@ -661,6 +703,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
             check_batch_lookup_args(requests, prompt_lookup_num_tokens, max_matching_ngram_size, K.APPEND_T_MAX, K.NGRAM_MAX, do_sample,
                                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                                     bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens, min_new_tokens=min_new_tokens)
+            check_batch_constraint_args(requests, constraint, self.lm_head.weight.shape[0], prompt_lookup_num_tokens)
             lplan = check_logits_args(stop_sequences=stop_sequences, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
                                       vocab_size=self.lm_head.weight.shape[0])
             return self._generate_batch_lookup(requests, budgets, max_batch_size, eos_token_id, pad_token_id,
@@ -674,9 +717,11 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                                   stop_sequences, stopping_criteria, eos_token_id, V)
         rplan = check_request_params(requests, do_sample, temperature, top_k, top_p, seed, repetition_penalty, no_repeat_ngram_size,
                                      bad_words_ids, suppress_tokens, min_new_tokens, stop_sequences, stopping_criteria, eos_token_id, V)
+        cplan = check_batch_constraint_args(requests, constraint, V, None, no_repeat_ngram_size, bad_words_ids, suppress_tokens,
+                                            min_new_tokens)
         if rplan.per_request:
             return self._generate_batch_rows(rplan, requests, budgets, max_batch_size, eos_token_id, pad_token_id, seed,
-                                             return_dict_in_generate)
+                                             return_dict_in_generate, cplan)
         sched = SlotScheduler(budgets, max_batch_size)
         if not requests:
             return BatchOutput([], [] if do_sample else None, sched) if return_dict_in_generate else []
@@ -698,6 +743,9 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         bad = K.seq_table(lplan.bad, dev) if lplan is not None else None
         stop = K.seq_table(lplan.stops, dev) if lplan is not None else None
         process = lplan is not None and lplan.process
+        ctab = None
+        if cplan is not None:
+            ctab, st.cstate = K.constraint_table(cplan.merged, dev), torch.full((B,), -1, **i32)
         pad = eos_token_id if pad_token_id is None else pad_token_id
         if do_sample:
             seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())        # as generate()
@@ -713,9 +761,14 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                     group = [(r, s) for r, s in admitted if (requests[r].get("images") is not None) == with_images]
                     if group:
                         self._admit(requests, budgets, group, st)
+                if ctab is not None and admitted:
+                    meta = torch.tensor([[s for _, s in admitted], [cplan.starts[r] for r, _ in admitted]], dtype=torch.int32).to(dev)
+                    st.cstate[meta[0]] = meta[1]                 # int32 indices: no cast launch
                 if process:
                     K.logits_process_(st.logits, st.hist, st.n_hist, st.n_gen, lplan.penalty, lplan.ngram, bad, lplan.min_new,
                                       eos_token_id)
+                if ctab is not None:
+                    K.constrain_mask_(st.logits, st.cstate, ctab, eos_token_id)
                 if do_sample:
                     K.request_uniform(seed, st.req_id, st.n_gen, out=u)
                     nxt = K.sample(st.logits, u, temperature, top_k, top_p, stats=want_lp)
@@ -727,6 +780,8 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                 else:
                     nxt = K.row_argmax(st.logits)
                 K.gen_push_stop_(nxt, st.done, st.hist, st.n_hist, st.n_prompt, st.n_gen, eos_token_id, pad, stop)
+                if ctab is not None:
+                    K.constrain_advance_(nxt, st.done, st.cstate, ctab)
                 blk = torch.stack([nxt, st.done] + ([lp.view(torch.int32)] if want_lp else [])).cpu()       # the step's one read-back
                 live = sched.live
                 for s, r in live.items():
@@ -755,7 +810,8 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         return BatchOutput(seqs, logprobs, sched)
 
     @torch.no_grad()
-    def _generate_batch_rows(self, rplan, requests, budgets, max_batch_size, eos_token_id, pad_token_id, seed, return_dict_in_generate):
+    def _generate_batch_rows(self, rplan, requests, budgets, max_batch_size, eos_token_id, pad_token_id, seed, return_dict_in_generate,
+                             cplan=None):
         """generate_batch when some request carries `params` (`rplan`: generation.check_request_params).  The loop, the scheduler, the
         admission and the state are generate_batch's; the slots' parameters live in one field-major device table [fields, B] int32
         (floats bit-cast; generation.RequestPlan.TABLE_FIELDS), every field a contiguous [B] array that the per-row kernels read:
@@ -766,7 +822,11 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                  lmod_gen_push_stop_rows, the read-back, the decode step.
         The launches of a step depend on the call (`rplan`'s three flags), never on which requests sit in the slots.  The
         log-probability of a token: x[t] / T - lse - log(kept fraction) under the row's own warp; a greedy row has T = 1 and keeps
-        everything, so its entry is x[t] - logsumexp(x) of the processed logits."""
+        everything, so its entry is x[t] - logsumexp(x) of the processed logits.
+        cplan (generation.ConstraintPlan; None: nothing below exists): the slots' automaton states `cstate` [B] int32 sit in the same
+        allocation behind the table (an array of their own, not a table column; -1 until a constrained request is admitted), so
+        the admitted slots' start states travel in the admission's one host -> device copy and land with its one indexed copy;
+        every step then runs lmod_constrain_mask_rows_bf16 after the processors and lmod_constrain_advance_rows after the push."""
         from ...constants import IMAGE_TOKEN_INDEX
         from ...generation import BatchOutput, RequestPlan, SlotScheduler
         sched = SlotScheduler(budgets, max_batch_size)
@@ -786,7 +846,13 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
             done=torch.ones(B, **i32), req_id=torch.full((B,), -1, **i32),
             logits=torch.zeros((B, V), device=dev, dtype=BF16))
         st.tab = K.ptr_table(st.cache.tensors())
-        table = torch.tensor(RequestPlan.neutral_table(B), dtype=torch.int32).to(dev)
+        ctab = cstate = None
+        if cplan is None:
+            table = torch.tensor(RequestPlan.neutral_table(B), dtype=torch.int32).to(dev)
+        else:
+            n_tab = RequestPlan.TABLE_ROWS * B
+            buf = torch.tensor([v for r in RequestPlan.neutral_table(B) for v in r] + [-1] * B, dtype=torch.int32).to(dev)
+            table, cstate, ctab = buf[:n_tab].view(RequestPlan.TABLE_ROWS, B), buf[n_tab:], K.constraint_table(cplan.merged, dev)
         row = RequestPlan.row_of
         p_seed = table[0:2].view(-1).view(torch.int64)                                # [B] 64-bit keys
         p_ctr0, p_greedy, p_topk = table[row("ctr0")], table[row("greedy")], table[row("top_k")]
@@ -808,12 +874,19 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                     group = [(r, s) for r, s in admitted if (requests[r].get("images") is not None) == with_images]
                     if group:
                         self._admit(requests, budgets, group, st)
-                if admitted:
+                if admitted and ctab is None:
                     cols = torch.tensor(rplan.columns(admitted, B, seed), dtype=torch.int32).to(dev)
                     table.view(-1)[cols[0]] = cols[1]                      # int32 indices: no cast launch
+                elif admitted:
+                    idx, val = rplan.columns(admitted, B, seed)
+                    cols = torch.tensor([idx + [n_tab + s for _, s in admitted], val + [cplan.starts[r] for r, _ in admitted]],
+                                        dtype=torch.int32).to(dev)
+                    buf[cols[0]] = cols[1]                                 # the table entries and the start states, one copy
                 if rplan.any_process:
                     K.logits_process_rows_(st.logits, st.hist, st.n_hist, st.n_gen, p_pen, p_ngram, p_minnew, rplan.any_penalty, bad,
                                            eos_token_id)
+                if ctab is not None:
+                    K.constrain_mask_(st.logits, cstate, ctab, eos_token_id)
                 if rplan.any_sample:
                     K.request_uniform_rows(p_seed, p_ctr0, st.n_gen, out=u)
                 nxt, stats = K.sample_rows(st.logits, u, p_temp, p_topk, p_topp, p_greedy, stats=True)
@@ -821,6 +894,8 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                 lp = (x - stats[:, 0].double() - torch.log(stats[:, 1].double())).clamp(max=0.0).float()
                 K.gen_push_stop_rows_(nxt, st.done, st.hist, st.n_hist, st.n_prompt, st.n_gen, eos_token_id, pad, stop,
                                       rplan.n_call_stops, p_first, p_count)
+                if ctab is not None:
+                    K.constrain_advance_(nxt, st.done, cstate, ctab)
                 blk = torch.stack([nxt, st.done, lp.view(torch.int32)]).cpu()                 # the step's one read-back
                 live = sched.live
                 for s, r in live.items():

@@ -72,6 +72,14 @@ offer is all that is accepted) and lookup_forced (model.assisted_force_accept). 
 decode steps), prefill passes, accepted drafts and the spread between repetitions.  One JSON line.
 
     python tools/bench_generate.py --only none --batched 24 --lookup 4 --max-batch-size 8 >> profiles/batched_lookup.jsonl
+
+--constraint times greedy generate(constraint=...) against plain greedy at B in {1, 8}, three arms alternating call by call in one
+process, one warm-up each, every repetition kept: plain (no constraint: the loop that ran before constraints existed), closed
+(TokenConstraint.from_allowed_tokens of 4 tokens: every row sits in a closed state, so lmod_constrain_mask_rows_bf16 sweeps the
+whole row every step) and open (a one-state open automaton that bans nothing: the two launches without a sweep).  ms per new token
+as above, (t(N2) - t(N1)) / (N2 - N1).  One JSON line per B.
+
+    python tools/bench_generate.py --only none --constraint > profiles/constrained_decoding.jsonl
 """
 import argparse
 import json
@@ -416,6 +424,44 @@ def processor_arms(model, Bs, text_len, reps, n1, n2, device_only=False):
         print(json.dumps(rec), flush=True)
 
 
+CONSTRAINT_ALLOWED = [32, 33, 34, 35]
+
+
+def constraint_arms(model, Bs, text_len, reps, n1, n2):
+    """ms per new token of greedy generate(): plain, under a closed allow-list of 4 tokens, under an open automaton that bans nothing."""
+    from llavamod.generation import TokenConstraint
+    cons = {"plain": None, "closed": TokenConstraint.from_allowed_tokens(CONSTRAINT_ALLOWED), "open": TokenConstraint(1, [], [], default=0)}
+
+    def run(pr, arm, n_new):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        kw = {} if cons[arm] is None else dict(constraint=cons[arm])
+        e0.record()
+        out = model.generate(**pr, max_new_tokens=n_new, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        assert out.shape[1] == n_new, out.shape                    # no EOS and no terminal state: every call runs its full length
+        assert arm != "closed" or set(out.reshape(-1).tolist()) <= set(CONSTRAINT_ALLOWED)
+        return e0.elapsed_time(e1)
+
+    for B in Bs:
+        pr = prompts(B, text_len)
+        t1, t2 = {a: [] for a in cons}, {a: [] for a in cons}
+        for rep in range(reps + 1):                                # rep 0 warms every arm at both lengths
+            for a in cons:
+                x, y = run(pr, a, n1), run(pr, a, n2)
+                if rep:
+                    t1[a].append(x)
+                    t2[a].append(y)
+        rec = {"metric": "generate_constraint_ms_per_new_token", "B": B, "V": model.lm_head.weight.shape[0],
+               "closed_allowed_tokens": len(CONSTRAINT_ALLOWED), "prompt_positions": text_len - 1 + 576, "n1": n1, "n2": n2}
+        for a in cons:
+            per = [(y - x) / (n2 - n1) for x, y in zip(t1[a], t2[a])]
+            rec[f"ms_per_token_{a}"] = round(min(per), 3)
+            rec[f"ms_per_token_{a}_all"] = [round(v, 3) for v in per]
+            rec[f"spread_{a}"] = round(max(per) / min(per) - 1, 4)
+        print(json.dumps(rec), flush=True)
+
+
 def batched_arms(model, n_req, B, text_len, reps, n1, n2, seed=0):
     """Wall ms of serving one request list: generate_batch / static batches of generate() / a B = 1 loop, and the scheduler's prediction."""
     import random
@@ -550,6 +596,8 @@ def main():
     ap.add_argument("--max-batch-size", type=int, default=8, help="slots of the --batched arms")
     ap.add_argument("--speculative", type=int, default=None, help="k: speculative sampling (student draft / forced) against do_sample")
     ap.add_argument("--lookup", type=int, default=None, help="k: prompt-lookup decoding (as is / acceptance forced) against greedy; with --batched: the generate_batch arms")
+    ap.add_argument("--constraint", action="store_true", help="greedy under a token automaton: plain / closed allow-list / open")
+    ap.add_argument("--constraint-only", default=None, help="comma-separated B of the constraint arms (default 1,8)")
     ap.add_argument("--spec-kernel-only", type=int, default=None, help="k: lmod_spec_sample_bf16 alone, no model (for a kernel trace)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate.py measures on the GPU"
@@ -591,6 +639,9 @@ def main():
     if a.processors:
         processor_arms(model, [int(x) for x in a.processors_only.split(",")] if a.processors_only else [1, 8], a.text_len, a.reps,
                        a.n1, a.n2, a.device_arm_only)
+    if a.constraint:
+        constraint_arms(model, [int(x) for x in a.constraint_only.split(",")] if a.constraint_only else [1, 8], a.text_len, a.reps,
+                        a.n1, a.n2)
     if not a.sample:
         return
     arms = (True,) if a.device_arm_only else (True, False)
