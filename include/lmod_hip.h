@@ -441,12 +441,47 @@ int lmod_gen_push_stop_rows(int* tokens, int* done, int* hist, int ld_hist, int*
  *   earlier, or by this step's EOS / stop sequence) or with state[r] outside [0, n_states) is left as it is.  Otherwise
  *   ns = edge_next[e] when tokens[r] has an edge e in the state (binary search), else default_next[state[r]].  ns < 0 (the token
  *   left the automaton; with the mask applied only when the row had no allowed token left): done[r] = 1, the state stays.
- *   Otherwise state[r] = ns, and done[r] = 1 when ns is terminal: the row is finished by that token, as by a stop sequence. */
+ *   Otherwise state[r] = ns, and done[r] = 1 when ns is terminal: the row is finished by that token, as by a stop sequence.
+ *
+ * Drafting what the automaton forces (generate(constraint=, constraint_draft_tokens=k)): a draft-and-verify round that carries the
+ * automaton.  Both entry points: one thread per row, int32 and exact, plain vector stores, no atomics, no workspace; every index is
+ * checked and none clamped; 1 <= k < T_MAX (16), LMOD_EINVAL outside; R == 0 is a no-op; a null pointer (edge_tok / edge_next only
+ * when E == 0) is LMOD_EINVAL.  They do not depend on where a draft came from.
+ * A state s in [0, n_states) is FORCED when it is closed, not terminal, and the set lmod_constrain_mask_rows_bf16 would allow in it -
+ *   the edges with next >= 0 and 0 <= tok < V, plus eos where the state accepts and 0 <= eos < V - has exactly one element, and that
+ *   element is a listed edge (t, ns) and not eos.  The masked distribution of a forced state is a point mass at t.
+ * lmod_constrain_draft: pending [R] (the row's pending token, already emitted), state [R] (the state after that token), done [R].
+ *   Walk: s_0 = state[r]; while j < k and s_j is forced with edge (t, ns): draft[j] = t, s_{j+1} = ns (the edge list is scanned
+ *   linearly and left at the second allowed edge).  A terminal state is not forced, so the walk stops after a token that enters one.
+ *   Outputs: n_draft [R]; draft [R, k]: the run, then -1 (never equal to a target token); chunk [R, k+1]: pending, the run, then
+ *   pending again (lmod_ngram_draft's rule: a valid id for the embedding gather, rejected and rewound like a rejected draft);
+ *   vstate [R, k+1]: vstate[j] = s_j for j <= n_draft, the state that masks verification row j (the `state` argument of ONE
+ *   lmod_constrain_mask_rows_bf16 launch over the [R*(k+1), V] verification logits), -1 behind that and -1 at j = n_draft when s_j
+ *   is terminal.  A done row, or a row whose state is outside [0, n_states): n_draft 0, draft all -1, vstate all -1, chunk = pending
+ *   repeated.
+ * lmod_constrain_accept: lmod_spec_accept's contract with the automaton and a budget, cut on the device.  draft [R, k], target
+ *   [R, k+1] (the argmax of the masked verification rows), done [R] (in/out), state [R] (in: after pending; out: after the last
+ *   emitted token), n_gen [R] (in/out: tokens the row has emitted), budget (max_new_tokens), lens_target [R] (in: L0 + k + 1, as
+ *   the verification pass left it).  A live row: n_acc = the longest prefix with draft[j] == target[j]; the candidates
+ *   draft[0:n_acc] then target[n_acc] are emitted in order, n_gen advancing by one each, and after each emitted token, tested in this
+ *   order: (1) it is eos (eos >= 0): done, the state stays; (2) it has no edge and no default (ns < 0, lmod_constrain_advance_rows's
+ *   rule): done, the state stays; otherwise state = ns, and (3) ns terminal: done; (4) n_gen == budget: done.  Emission stops at the
+ *   first token that sets done.  A row whose state is outside [0, n_states) is unconstrained: rules (1) and (4) only.
+ *   lens_target[r] = L0 + n_emit: the cache holds the prompt and every emitted token but the last (lmod_batch_lookup_round's
+ *   invariant).  A row done at entry emits nothing: n_acc = n_emit = 0, next = pad, lens_target[r] = L0; state and n_gen untouched.
+ *   out [R, k+5]: lmod_spec_accept's columns - 0..k the emitted tokens then pad, k+1 n_acc, k+2 n_emit, k+3 the next pending token
+ *   (the last emitted one; pad once done), k+4 done; next_token [R] = column k+3. */
 int lmod_constrain_mask_rows_bf16(void* logits, long long ld, int V, int R, const int* state, const int* edge_off, const int* edge_tok,
                                   const int* edge_next, const int* default_next, const int* flags, int n_states, int eos,
                                   hipStream_t stream);
 int lmod_constrain_advance_rows(const int* tokens, int* done, int* state, const int* edge_off, const int* edge_tok, const int* edge_next,
                                 const int* default_next, const int* flags, int n_states, int R, hipStream_t stream);
+int lmod_constrain_draft(const int* pending, const int* state, const int* done, const int* edge_off, const int* edge_tok,
+                         const int* edge_next, const int* default_next, const int* flags, int n_states, int eos, int V, int k, int* draft,
+                         int* chunk, int* vstate, int* n_draft, int R, hipStream_t stream);
+int lmod_constrain_accept(const int* draft, const int* target, int k, int* done, int* state, const int* edge_off, const int* edge_tok,
+                          const int* edge_next, const int* default_next, const int* flags, int n_states, int eos, int pad, int* n_gen,
+                          int budget, int* lens_target, int* out, int* next_token, int R, hipStream_t stream);
 
 /* ---- continuous batching (generate_batch(): a finished slot of the running batch is refilled while the others keep decoding;
  *      csrc/batch.hip) -------------------------------------------------------------------------------------------------------

@@ -20,10 +20,23 @@
 // state follows its token's edge (binary search; default_next when the token is not listed).  A token that leaves the automaton
 // (next < 0: possible only when the row had no allowed token left) finishes the row and keeps its state; entering a terminal state
 // finishes the row by that token, as a stop-sequence match does.
+//
+// generate(constraint=, constraint_draft_tokens=k) drafts what the automaton FORCES.  A state is FORCED when it is closed, not
+// terminal, and the set the mask would allow in it is one listed edge (t, ns) with t != eos: exactly one edge with next >= 0 and
+// 0 <= tok < V, and no eos beside it (the state does not accept, or eos is outside [0, V)).  The masked distribution is then a point
+// mass at t, so a run of forced states is a draft that needs no drafter.  Both kernels below: one thread per row, int32 and exact, no
+// atomics, no workspace, every index checked and none clamped.
+//   lmod_constrain_draft   walks the forced run from the row's state (at most k tokens; a linear scan of the state's edges that
+//                          leaves at the second allowed one) and writes the draft, the verification chunk and the state that
+//                          masks each verification row;
+//   lmod_constrain_accept  lmod_spec_accept's rule and block with the automaton, EOS and the token budget applied to every emitted
+//                          token on the device: the row's state, done flag, counter and cache length come out as plain
+//                          constrained greedy would leave them.
 #include "common.h"
 
 #define CONSTRAIN_THREADS 256
 #define CONSTRAIN_LDS_MAX 65536                  // logits.hip's LOGITS_LDS_MAX: V <= 524288
+#define CONSTRAIN_T_MAX 16                       // APPEND_T_MAX of csrc/append.hip: the verification chunk holds k + 1 <= 16 tokens
 #define BF16_NEG_INF ((bf16_t)0xff80u)
 #define FLAG_ACCEPT 1
 #define FLAG_TERMINAL 2
@@ -115,6 +128,101 @@ __global__ __launch_bounds__(CONSTRAIN_THREADS) void constrain_advance_rows_kern
   if (t.flags[ns] & FLAG_TERMINAL) done[r] = 1;
 }
 
+// The single allowed edge of state s, when s is forced: true, and (*tok, *ns) is the edge.  s must be inside [0, n_states).
+__device__ __forceinline__ bool constrain_forced(const ConstrainTables& t, int s, int eos, int V, int* tok, int* ns) {
+  const int fl = t.flags[s];
+  if (t.default_next[s] >= 0 || (fl & FLAG_TERMINAL)) return false;      // open, or nothing left to emit
+  if ((fl & FLAG_ACCEPT) && eos >= 0 && eos < V) return false;           // eos is allowed beside whatever the edges allow
+  int n = 0, ft = -1, fn = -1;
+  for (int e = t.edge_off[s], e1 = t.edge_off[s + 1]; e < e1; ++e) {
+    const int nx = t.edge_next[e], tk = t.edge_tok[e];
+    if (nx < 0 || tk < 0 || tk >= V) continue;
+    if (++n > 1) return false;
+    ft = tk; fn = nx;
+  }
+  if (n != 1 || ft == eos || fn >= t.n_states) return false;
+  *tok = ft; *ns = fn;
+  return true;
+}
+
+__global__ __launch_bounds__(CONSTRAIN_THREADS) void constrain_draft_kernel(const int* __restrict__ pending, const int* __restrict__ state,
+                                                                            const int* __restrict__ done, ConstrainTables t, int eos,
+                                                                            int V, int k, int* __restrict__ draft, int* __restrict__ chunk,
+                                                                            int* __restrict__ vstate, int* __restrict__ n_draft, int R) {
+  const int r = blockIdx.x * CONSTRAIN_THREADS + threadIdx.x;
+  if (r >= R) return;
+  int* dr = draft + (long long)r * k;
+  int* ch = chunk + (long long)r * (k + 1);
+  int* vs = vstate + (long long)r * (k + 1);
+  const int pend = pending[r];
+  int s = state[r];
+  const bool live = done[r] == 0 && s >= 0 && s < t.n_states;
+  ch[0] = pend;
+  int nd = 0;
+  if (live) {
+    int tok, ns;
+    while (nd < k && constrain_forced(t, s, eos, V, &tok, &ns)) {
+      vs[nd] = s;
+      dr[nd] = tok;
+      ch[nd + 1] = tok;
+      s = ns;
+      ++nd;
+    }
+    vs[nd] = (t.flags[s] & FLAG_TERMINAL) ? -1 : s;                       // the row behind the run: masked by where the run ended
+  }
+  for (int j = nd; j < k; ++j) { dr[j] = -1; ch[j + 1] = pend; }
+  for (int j = live ? nd + 1 : 0; j <= k; ++j) vs[j] = -1;
+  n_draft[r] = nd;
+}
+
+__global__ __launch_bounds__(CONSTRAIN_THREADS) void constrain_accept_kernel(const int* __restrict__ draft, const int* __restrict__ target,
+                                                                             int k, int* __restrict__ done, int* __restrict__ state,
+                                                                             ConstrainTables t, int eos, int pad, int* __restrict__ n_gen,
+                                                                             int budget, int* __restrict__ lens_target,
+                                                                             int* __restrict__ out, int* __restrict__ next_token, int R) {
+  const int r = blockIdx.x * CONSTRAIN_THREADS + threadIdx.x;
+  if (r >= R) return;
+  const int* dr = draft + (long long)r * k;
+  const int* tg = target + (long long)r * (k + 1);
+  int* o = out + (long long)r * (k + 5);
+  const int len0 = lens_target[r] - (k + 1);                              // the cache before the verification pass
+  int n_acc = 0, n_emit = 0, fin = 1, last = pad;
+  if (done[r] == 0) {
+    while (n_acc < k && dr[n_acc] == tg[n_acc]) ++n_acc;
+    int s = state[r], ng = n_gen[r];
+    const bool inside = s >= 0 && s < t.n_states;                         // outside: an unconstrained row, eos and the budget only
+    fin = 0;
+    while (!fin && n_emit <= n_acc) {
+      const int tok = n_emit < n_acc ? dr[n_emit] : tg[n_acc];
+      o[n_emit++] = tok;
+      last = tok;
+      ++ng;
+      if (eos >= 0 && tok == eos) { fin = 1; break; }                     // the state stays, as after lmod_gen_push_stop's EOS
+      if (inside) {
+        int lo = t.edge_off[s], hi = t.edge_off[s + 1];                   // the first edge whose token is >= tok
+        const int end = hi;
+        while (lo < hi) {
+          const int mid = lo + ((hi - lo) >> 1);
+          if (t.edge_tok[mid] < tok) lo = mid + 1; else hi = mid;
+        }
+        const int ns = (lo < end && t.edge_tok[lo] == tok) ? t.edge_next[lo] : t.default_next[s];
+        if (ns < 0 || ns >= t.n_states) { fin = 1; break; }               // the token left the automaton: the state stays
+        s = ns;
+        if (t.flags[ns] & FLAG_TERMINAL) fin = 1;
+      }
+      if (ng >= budget) fin = 1;
+    }
+    state[r] = s;
+    n_gen[r] = ng;
+  }
+  for (int i = n_emit; i <= k; ++i) o[i] = pad;
+  const int nxt = fin ? pad : last;
+  o[k + 1] = n_acc; o[k + 2] = n_emit; o[k + 3] = nxt; o[k + 4] = fin;
+  next_token[r] = nxt;
+  done[r] = fin;
+  lens_target[r] = len0 + n_emit;
+}
+
 extern "C" {
 
 int lmod_constrain_mask_rows_bf16(void* logits, long long ld, int V, int R, const int* state, const int* edge_off, const int* edge_tok,
@@ -139,6 +247,31 @@ int lmod_constrain_advance_rows(const int* tokens, int* done, int* state, const 
   ConstrainTables t = {edge_off, edge_tok, edge_next, default_next, flags, n_states};
   hipLaunchKernelGGL(constrain_advance_rows_kernel, dim3((R + CONSTRAIN_THREADS - 1) / CONSTRAIN_THREADS), dim3(CONSTRAIN_THREADS), 0,
                      stream, tokens, done, state, t, R);
+  return lmod_launch_status();
+}
+
+int lmod_constrain_draft(const int* pending, const int* state, const int* done, const int* edge_off, const int* edge_tok,
+                         const int* edge_next, const int* default_next, const int* flags, int n_states, int eos, int V, int k, int* draft,
+                         int* chunk, int* vstate, int* n_draft, int R, hipStream_t stream) {
+  if (R < 0 || n_states < 1 || V < 1 || k < 1 || k >= CONSTRAIN_T_MAX) return LMOD_EINVAL;
+  if (R == 0) return LMOD_OK;
+  if (!pending || !state || !done || !edge_off || !default_next || !flags || !draft || !chunk || !vstate || !n_draft) return LMOD_EINVAL;
+  ConstrainTables t = {edge_off, edge_tok, edge_next, default_next, flags, n_states};
+  hipLaunchKernelGGL(constrain_draft_kernel, dim3((R + CONSTRAIN_THREADS - 1) / CONSTRAIN_THREADS), dim3(CONSTRAIN_THREADS), 0, stream,
+                     pending, state, done, t, eos, V, k, draft, chunk, vstate, n_draft, R);
+  return lmod_launch_status();
+}
+
+int lmod_constrain_accept(const int* draft, const int* target, int k, int* done, int* state, const int* edge_off, const int* edge_tok,
+                          const int* edge_next, const int* default_next, const int* flags, int n_states, int eos, int pad, int* n_gen,
+                          int budget, int* lens_target, int* out, int* next_token, int R, hipStream_t stream) {
+  if (R < 0 || n_states < 1 || k < 1 || k >= CONSTRAIN_T_MAX) return LMOD_EINVAL;
+  if (R == 0) return LMOD_OK;
+  if (!draft || !target || !done || !state || !edge_off || !default_next || !flags || !n_gen || !lens_target || !out || !next_token)
+    return LMOD_EINVAL;
+  ConstrainTables t = {edge_off, edge_tok, edge_next, default_next, flags, n_states};
+  hipLaunchKernelGGL(constrain_accept_kernel, dim3((R + CONSTRAIN_THREADS - 1) / CONSTRAIN_THREADS), dim3(CONSTRAIN_THREADS), 0, stream,
+                     draft, target, k, done, state, t, eos, pad, n_gen, budget, lens_target, out, next_token, R);
   return lmod_launch_status();
 }
 

@@ -68,6 +68,8 @@ SIGNATURES = {
     "lmod_gen_push_stop_rows": "pp" + "pipp" + "p" + "ii" + "pp" + "ii" + "pp" + "i" + "p",
     "lmod_constrain_mask_rows_bf16": "pqii" + "p" + "ppppp" + "ii" + "p",
     "lmod_constrain_advance_rows": "ppp" + "ppppp" + "ii" + "p",
+    "lmod_constrain_draft": "ppp" + "ppppp" + "iiii" + "pppp" + "i" + "p",
+    "lmod_constrain_accept": "pp" + "i" + "pp" + "ppppp" + "iii" + "p" + "i" + "ppp" + "i" + "p",
     "lmod_kv_admit_rows": "pp" + "i" + "pp" + "iiiiii" + "p",
     "lmod_slot_admit": "p" + "pippp" + "ii" + "pipppppp" + "p",
     "lmod_request_uniform": "Q" + "ppp" + "i" + "p",

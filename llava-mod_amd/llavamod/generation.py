@@ -194,11 +194,12 @@ class AssistedOutput:
     """`generate(assistant_model=..., return_dict_in_generate=True)`: sequences int64 [B, L] (new tokens only), num_rounds (draft /
     verify rounds), num_target_forwards (the prefill plus one verification pass per round), num_accepted int64 [B] (draft tokens that
     were emitted) and the target's KV cache (when max_new_tokens cut the last round short it holds accepted tokens behind the
-    returned ones)."""
+    returned ones).  With `generate(constraint=..., constraint_draft_tokens=k)`: constraint_states int32 [B], every row's final automaton
+    state (None otherwise), and the cache holds the prompt and every returned token but each row's last."""
 
-    def __init__(self, sequences, num_rounds, num_target_forwards, num_accepted, past_key_values=None):
+    def __init__(self, sequences, num_rounds, num_target_forwards, num_accepted, past_key_values=None, constraint_states=None):
         self.sequences, self.num_rounds, self.num_target_forwards = sequences, num_rounds, num_target_forwards
-        self.num_accepted, self.past_key_values = num_accepted, past_key_values
+        self.num_accepted, self.past_key_values, self.constraint_states = num_accepted, past_key_values, constraint_states
 
 
 def check_assisted_args(do_sample, num_beams, num_assistant_tokens, t_max, num_return_sequences=1):
@@ -1001,6 +1002,22 @@ class TokenConstraint:
             s = nx
         return s, True
 
+    def forced(self, state, eos=None, vocab_size=None):
+        """The token `state` forces, as (token, next), or None - what lmod_constrain_draft drafts from it.  A state is FORCED when
+        it is closed, not terminal, and the set the mask would allow in it - the edges with next >= 0 and 0 <= token < vocab_size
+        (None: no upper bound), plus `eos` where the state accepts (None: no such token) - has exactly one element, and that element
+        is a listed edge, not eos.  generate(constraint_draft_tokens=k) emits up to k consecutive forced tokens per pass."""
+        if not 0 <= state < self.n_states or self.default_next[state] >= 0 or self.terminal[state]:
+            return None
+        inside = lambda tok: tok >= 0 and (vocab_size is None or tok < vocab_size)
+        if self.accept[state] and eos is not None and inside(eos):
+            return None
+        allowed = [(self.edge_tok[e], self.edge_next[e]) for e in range(self.edge_off[state], self.edge_off[state + 1])
+                   if self.edge_next[e] >= 0 and inside(self.edge_tok[e])]
+        if len(allowed) != 1 or (eos is not None and allowed[0][0] == eos):
+            return None
+        return allowed[0]
+
     def __repr__(self):
         return f"TokenConstraint(n_states={self.n_states}, edges={len(self.edge_tok)}, start={self.start})"
 
@@ -1057,6 +1074,40 @@ def check_constraint_args(constraint, vocab_size, num_beams=1, assistant_model=N
     used = _banning(no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens)
     if used:
         raise ValueError(_BANNING_MSG.format(used=", ".join(used)))
+
+
+def check_constraint_draft_args(constraint_draft_tokens, constraint, t_max, do_sample=False, num_beams=1, num_return_sequences=1,
+                                assistant_model=None, speculative_sampling=False, prompt_lookup_num_tokens=None,
+                                repetition_penalty=1.0, stop_sequences=None, stopping_criteria=None):
+    """`generate(constraint=c, constraint_draft_tokens=k)` beside its other arguments; nothing to check without the argument.
+    ValueError, before any device work: no constraint; k not an int in 1..t_max-1 (the verification chunk holds k + 1 tokens);
+    do_sample, num_beams > 1, num_return_sequences > 1 (greedy, one sequence per prompt); assistant_model, speculative_sampling,
+    prompt_lookup_num_tokens (another drafter); repetition_penalty != 1, stop_sequences, stopping_criteria (the round verifies
+    logits that only the constraint's mask has touched).  The banning processors are refused with any constraint
+    (`check_constraint_args`)."""
+    k = constraint_draft_tokens
+    if k is None:
+        return
+    if constraint is None:
+        raise ValueError("constraint_draft_tokens needs a constraint: it drafts the tokens the automaton forces")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= t_max - 1:
+        raise ValueError(f"constraint_draft_tokens must be an int in 1..{t_max - 1}, got {k!r}")
+    if do_sample or num_beams != 1:
+        raise ValueError("constraint_draft_tokens supports greedy decoding only: do_sample=True and num_beams > 1 cannot be combined "
+                         "with it")
+    if num_return_sequences != 1:
+        raise ValueError("constraint_draft_tokens returns one sequence per prompt: num_return_sequences must be 1")
+    modes = {"assistant_model": assistant_model is not None, "speculative_sampling": bool(speculative_sampling),
+             "prompt_lookup_num_tokens": prompt_lookup_num_tokens is not None}
+    used = [n for n, v in modes.items() if v]
+    if used:
+        raise ValueError(f"constraint_draft_tokens drafts from the automaton: it cannot be combined with {', '.join(used)}")
+    given = {"repetition_penalty": repetition_penalty not in (1.0, None), "stop_sequences": stop_sequences is not None,
+             "stopping_criteria": stopping_criteria is not None}
+    used = [n for n, v in given.items() if v]
+    if used:
+        raise ValueError(f"{', '.join(used)} cannot be combined with constraint_draft_tokens: the round verifies logits that only the "
+                         "constraint's mask has touched")
 
 
 class ConstraintPlan:

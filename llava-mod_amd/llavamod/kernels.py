@@ -748,6 +748,46 @@ def constrain_advance_(tokens, done, state, table):
     call("lmod_constrain_advance_rows", ptr(tokens), ptr(done), ptr(state), *_constraint_args(table, state, R), R)
 
 
+def constrain_draft(pending, state, done, table, k, eos, V, out=None):
+    """The run of tokens the automaton forces on every row (lmod_constrain_draft in include/lmod_hip.h).  pending / state / done [R]:
+    device int32, the row's pending token and the state after it.  Returns (draft [R, k]: the run then -1, chunk [R, k+1]: pending,
+    the run, pending again, vstate [R, k+1]: the state that masks each verification row, -1 behind the run, n_draft [R]); out: the
+    four tensors to reuse.  k outside 1..APPEND_T_MAX-1 raises (LMOD_EINVAL)."""
+    R = pending.numel()
+    for t in (pending, done):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == R
+    args = _constraint_args(table, state, R)
+    k = int(k)
+    if out is None:
+        out = (torch.empty((R, max(k, 0)), device=pending.device, dtype=torch.int32),
+               torch.empty((R, max(k, 0) + 1), device=pending.device, dtype=torch.int32),
+               torch.empty((R, max(k, 0) + 1), device=pending.device, dtype=torch.int32),
+               torch.empty(R, device=pending.device, dtype=torch.int32))
+    draft, chunk, vstate, n_draft = out
+    assert all(t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() for t in out)
+    assert (k < 1 or (tuple(draft.shape) == (R, k) and tuple(chunk.shape) == (R, k + 1) and tuple(vstate.shape) == (R, k + 1)))
+    assert n_draft.numel() == R
+    call("lmod_constrain_draft", ptr(pending), ptr(state), ptr(done), *args, -1 if eos is None else int(eos), int(V), k, ptr(draft),
+         ptr(chunk), ptr(vstate), ptr(n_draft), R)
+    return draft, chunk, vstate, n_draft
+
+
+def constrain_accept(draft, target, done, state, table, eos, pad, n_gen, budget, lens_target):
+    """One constrained draft-and-verify round's acceptance on the device (lmod_constrain_accept): `spec_accept`'s rule and block with
+    every emitted token followed through the automaton and cut at EOS, a token that leaves the automaton, a terminal state or
+    `budget` tokens.  draft [R, k], target [R, k+1], done / state / n_gen / lens_target [R]: device int32, contiguous; the last four
+    are updated in place.  Returns (block [R, k+5] int32: emitted tokens | n_acc | n_emitted | next_token | done, next_token [R])."""
+    R, k = draft.shape
+    for t in (draft, target, done, n_gen, lens_target):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert tuple(target.shape) == (R, k + 1) and done.numel() == R and n_gen.numel() == R and lens_target.numel() == R
+    out = torch.empty((R, k + 5), device=draft.device, dtype=torch.int32)
+    nxt = torch.empty(R, device=draft.device, dtype=torch.int32)
+    call("lmod_constrain_accept", ptr(draft), ptr(target), k, ptr(done), ptr(state), *_constraint_args(table, state, R),
+         -1 if eos is None else int(eos), 0 if pad is None else int(pad), ptr(n_gen), int(budget), ptr(lens_target), ptr(out), ptr(nxt), R)
+    return out, nxt
+
+
 # ------------------------------------------------------------------------------------------ prompt-lookup decoding
 NGRAM_MAX = 8              # csrc/lookup.hip: the longest trailing n-gram lmod_ngram_draft looks up
 

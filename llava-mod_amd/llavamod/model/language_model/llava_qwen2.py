@@ -371,7 +371,7 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
                  past_key_values=None, assistant_model=None, num_assistant_tokens=5, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, min_new_tokens=0, stop_sequences=None,
                  stopping_criteria=None, speculative_sampling=False, prompt_lookup_num_tokens=None, max_matching_ngram_size=2,
-                 constraint=None, **kwargs):
+                 constraint=None, constraint_draft_tokens=None, **kwargs):
         """Generation with a KV cache (the reference's eval path calls HF `generate` on the Eval model,
         llava_qwen2_moe.py:629-681; its serving code passes do_sample / temperature / top_p, its eval scripts num_beams).
         Greedy by default; do_sample=True draws from the temperature / top-k / top-p filtered distribution (`seed` makes the
@@ -440,12 +440,30 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         sequences work with it; num_beams > 1, assistant_model, speculative_sampling, prompt_lookup_num_tokens and the banning
         processors (no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens) raise ValueError.  With
         return_dict_in_generate the result carries `constraint_states` (int32 [rows]: the final states).  None: nothing new is
-        allocated or launched."""
+        allocated or launched.
+
+        constraint_draft_tokens = k (1..APPEND_T_MAX-1, with a constraint): greedy constrained decoding that drafts what the
+        automaton FORCES, `_constraint_draft_generate`.  Where a state allows a single token (`TokenConstraint.forced`: the rest of
+        "tabby cat" after "tabby", the fixed keys of a template) the masked distribution is a point mass, so every round drafts the
+        forced run behind the pending token (lmod_constrain_draft, up to k tokens), verifies it in one pass over the weights with
+        every verification row masked by its own state, and emits 1 to k + 1 tokens (lmod_constrain_accept).  The tokens and
+        `constraint_states` are those of generate(constraint=c) wherever the chunk and the decode path agree on the masked argmax
+        (away from ties).  Works with images and past_key_values; with return_dict_in_generate an `AssistedOutput` that carries
+        `constraint_states`.  Greedy only, one sequence per prompt: do_sample, num_beams > 1, num_return_sequences > 1,
+        assistant_model, speculative_sampling, prompt_lookup_num_tokens, repetition_penalty, stop_sequences and stopping_criteria
+        raise ValueError with it, and so does the argument without a constraint.  None: nothing new is allocated or launched."""
         from ...generation import check_logits_args
         if constraint is not None:
             from ...generation import check_constraint_args
             check_constraint_args(constraint, self.lm_head.weight.shape[0], num_beams, assistant_model, prompt_lookup_num_tokens,
                                   speculative_sampling, no_repeat_ngram_size, bad_words_ids, suppress_tokens, min_new_tokens)
+        if constraint_draft_tokens is not None:
+            from ...generation import check_constraint_draft_args
+            check_constraint_draft_args(constraint_draft_tokens, constraint, K.APPEND_T_MAX, do_sample, num_beams, num_return_sequences,
+                                        assistant_model, speculative_sampling, prompt_lookup_num_tokens, repetition_penalty,
+                                        stop_sequences, stopping_criteria)
+            return self._constraint_draft_generate(input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id,
+                                                   constraint, constraint_draft_tokens, return_dict_in_generate, past_key_values)
         if prompt_lookup_num_tokens is not None:
             from ...generation import check_prompt_lookup_args
             check_prompt_lookup_args(prompt_lookup_num_tokens, max_matching_ngram_size, K.APPEND_T_MAX, K.NGRAM_MAX, do_sample, num_beams,
@@ -1210,6 +1228,77 @@ class _CausalLMBase(nn.Module, LlavaMetaForCausalLM):
         seq = book.sequences().to(dev)
         if return_dict_in_generate:
             return AssistedOutput(seq, book.num_rounds, 1 + book.num_rounds, book.num_accepted.to(dev), cache)
+        return seq
+
+    @torch.no_grad()
+    def _constraint_draft_generate(self, input_ids, attention_mask, images, max_new_tokens, eos_token_id, pad_token_id, constraint, k,
+                                   return_dict_in_generate, past=None):
+        """Greedy constrained decoding that drafts the tokens the automaton forces, `generate(constraint=c,
+        constraint_draft_tokens=k)`: `_prompt_lookup_generate`'s round with the automaton carried through it, so there is no token
+        history and no lmod_hist_push_block.  The constraint's tables go to the device once; every row carries one int32 state and
+        one int32 count of emitted tokens.  The prefill logits are masked with the start state, then lmod_row_argmax_bf16 and
+        lmod_constrain_advance_rows: the first token may already end a row through a terminal state, so the host reads `done` back
+        once here.  Per round, always the same launches: (1) lmod_constrain_draft (the forced run behind the pending token, the
+        verification chunk, the state of every verification row); (2) the chunk's embeddings; (3) ONE forward_append with
+        T = k + 1 for every row, whether it has a draft or not; (4) the head; (5) ONE lmod_constrain_mask_rows_bf16 over the
+        B * (k+1) rows with the draft's states (-1 behind a run: those rows are never accepted); (6) lmod_row_argmax_bf16;
+        (7) lmod_constrain_accept (the longest matching prefix; every emitted token follows its edge and is cut at EOS, a token
+        that leaves the automaton, a terminal state or max_new_tokens; done, state, count and the cache's lens are written there);
+        (8) the round's one read-back, the [B, k+5] block.  Nothing goes from the host to the device inside the loop: the device
+        cuts, so the cache holds, as plain greedy's does, the prompt and every returned token but each row's last.  The result
+        equals generate(constraint=c) wherever the chunk and the decode path agree on the masked argmax (away from ties).  A MoE
+        model routes the B * (k+1) rows of a round with the eval capacity rule over the rows of that call.  `assisted_trace`
+        (measurement only) receives 4 events per round: start, after the draft, after the verification pass with its mask and
+        argmax, after accept / read-back.  Returns the new tokens [B, <= max_new_tokens]; with return_dict_in_generate an
+        `AssistedOutput` with `constraint_states`."""
+        from ...generation import AssistedBookkeeper, AssistedOutput
+        was_training = self.training
+        self.eval()
+        try:
+            cache, logits = self._start(input_ids, attention_mask, images, max_new_tokens + k + 1, past)
+            B, dev = logits.shape[0], logits.device
+            V = logits.shape[1]
+            ctab = K.constraint_table(constraint, dev)
+            cstate = torch.full((B,), constraint.start, device=dev, dtype=torch.int32)
+            book = AssistedBookkeeper(B, k, max_new_tokens, eos_token_id, eos_token_id if pad_token_id is None else pad_token_id)
+            K.constrain_mask_(logits, cstate, ctab, eos_token_id)
+            nxt = K.row_argmax(logits)
+            done = book.first(nxt).to(device=dev, dtype=torch.int32).contiguous()
+            K.constrain_advance_(nxt, done, cstate, ctab)
+            book.stopped |= done.cpu() != 0                                           # a terminal state behind the first token
+            done.copy_(book.stopped.to(torch.int32))                                  # ... and max_new_tokens == 1
+            n_gen = torch.ones(B, device=dev, dtype=torch.int32)
+            len0 = cache.lens.cpu().long()                                              # cache positions before the first new token
+            lt_h = len0.clone()
+            emb_w = self.model.embed_tokens.weight
+            bufs = (torch.empty((B, k), device=dev, dtype=torch.int32), torch.empty((B, k + 1), device=dev, dtype=torch.int32),
+                    torch.empty((B, k + 1), device=dev, dtype=torch.int32), torch.empty(B, device=dev, dtype=torch.int32))
+            trace = getattr(self, "assisted_trace", None)
+            mark = (lambda: None) if trace is None else (lambda: (ev.append(torch.cuda.Event(enable_timing=True)), ev[-1].record()))
+            while not book.finished:
+                ev = []
+                mark()
+                draft_t, chunk, vstate, _ = K.constrain_draft(nxt, cstate, done, ctab, k, eos_token_id, V, out=bufs)
+                mark()
+                if int(lt_h.max()) + k + 1 > cache.smax:
+                    cache.grow(int(lt_h.max()) + k + 1 + max_new_tokens)
+                hid = self.model.forward_append(K.gather_rows(emb_w, None, chunk.view(-1), emb_w.shape[1]), cache, k + 1,
+                                                max_len=int(lt_h.max()))
+                vlogits = K.constrain_mask_(ops.linear_fwd(hid, self.head()), vstate.view(-1), ctab, eos_token_id)
+                target = K.row_argmax(vlogits).view(B, k + 1)
+                mark()
+                block, nxt = K.constrain_accept(draft_t, target, done, cstate, ctab, eos_token_id, book.pad, n_gen, max_new_tokens,
+                                                cache.lens)
+                book.update(block.cpu())                                                # the round's one read-back
+                mark()
+                if trace is not None:
+                    trace.append(ev)
+                lt_h = len0 + book.n - 1                                                # what lmod_constrain_accept left in cache.lens
+        finally:
+            self.train(was_training)
+        seq = book.sequences().to(dev)
+        if return_dict_in_generate:
+            return AssistedOutput(seq, book.num_rounds, 1 + book.num_rounds, book.num_accepted.to(dev), cache, cstate)
         return seq
 
     @torch.no_grad()

@@ -80,6 +80,16 @@ whole row every step) and open (a one-state open automaton that bans nothing: th
 as above, (t(N2) - t(N1)) / (N2 - N1).  One JSON line per B.
 
     python tools/bench_generate.py --only none --constraint > profiles/constrained_decoding.jsonl
+
+--constraint-draft k times generate(constraint=c, constraint_draft_tokens=k) (every round drafts the tokens the automaton forces and
+verifies them in one pass) against generate(constraint=c) at B in {1, 8}, two arms alternating call by call in one process, one
+warm-up each, every repetition kept.  c is a from_choices trie over answers of 8 tokens with a forced tail of 0, 3 or 7 tokens
+(constraint_draft_tries); every call runs until its rows reach a terminal state.  per arm: ms per answer (the whole call, prefill
+included), passes over the weights per answer, and a one-token call (the prefill and the first token) to subtract; one more,
+untimed call splits the rounds into draft / verify / accept by events inside the loop (model.assisted_trace).  One JSON line per B
+and tail.
+
+    python tools/bench_generate.py --only none --constraint-draft 7 > profiles/constraint_draft.jsonl
 """
 import argparse
 import json
@@ -462,6 +472,68 @@ def constraint_arms(model, Bs, text_len, reps, n1, n2):
         print(json.dumps(rec), flush=True)
 
 
+CONSTRAINT_DRAFT_LEN = 8
+
+
+def constraint_draft_tries(tail):
+    """from_choices over answers of CONSTRAINT_DRAFT_LEN tokens: each of the first 8 - tail tokens is a choice between two ids (the
+    same two at every state of that depth), the last `tail` tokens are forced.  tail 0: every state branches, nothing can be drafted;
+    tail 3: the last branch is the fifth token; tail 7: only the first token is chosen.  Whatever the random weights choose, an
+    answer has the same shape."""
+    from llavamod.generation import TokenConstraint
+    n = CONSTRAINT_DRAFT_LEN
+    heads = [[]]
+    for d in range(n - tail):
+        heads = [h + [1000 + 2 * d + j] for h in heads for j in (0, 1)]
+    return TokenConstraint.from_choices([h + [2000 + d for d in range(tail)] for h in heads])
+
+
+def constraint_draft_arms(model, k, Bs, text_len, reps):
+    """ms and passes per answer: generate(constraint=c) against generate(constraint=c, constraint_draft_tokens=k)."""
+    n = CONSTRAINT_DRAFT_LEN
+
+    def run(pr, c, arm, n_new=n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        kw = dict(constraint_draft_tokens=k) if arm == "draft" else {}
+        e0.record()
+        out = model.generate(**pr, max_new_tokens=n_new, constraint=c, return_dict_in_generate=True, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        assert out.sequences.shape[1] == n_new, out.sequences.shape             # every row runs into its terminal state at token 8
+        passes = out.num_target_forwards if arm == "draft" else out.sequences.shape[1]
+        return e0.elapsed_time(e1), passes, out.sequences
+
+    for B in Bs:
+        pr = prompts(B, text_len)
+        for tail in (0, 3, 7):
+            c = constraint_draft_tries(tail)
+            ms, first, passes, same = {"plain": [], "draft": []}, {"plain": [], "draft": []}, {}, True
+            for rep in range(reps + 1):                            # rep 0 warms both arms
+                seqs = {}
+                for arm in ("plain", "draft"):
+                    t, passes[arm], seqs[arm] = run(pr, c, arm)
+                    t1 = run(pr, c, arm, 1)[0]
+                    if rep:
+                        ms[arm].append(t)
+                        first[arm].append(t1)
+                same = same and bool(torch.equal(seqs["plain"], seqs["draft"]))
+            rec = {"metric": "generate_constraint_draft_ms_per_answer", "B": B, "k": k, "answer_tokens": n, "forced_tail": tail,
+                   "states": c.n_states, "prompt_positions": text_len - 1 + 576, "same_tokens": same}
+            for arm in ("plain", "draft"):
+                rec[f"passes_{arm}"] = passes[arm]
+                rec[f"ms_per_answer_{arm}"] = round(min(ms[arm]), 2)
+                rec[f"ms_per_answer_{arm}_all"] = [round(v, 2) for v in ms[arm]]
+                rec[f"ms_first_token_call_{arm}_all"] = [round(v, 2) for v in first[arm]]
+                rec[f"ms_behind_first_token_{arm}"] = round(min(ms[arm]) - min(first[arm]), 2)
+            model.assisted_trace = []                              # one more, untimed call: the rounds' phases from events in the loop
+            run(pr, c, "draft")
+            ev, model.assisted_trace = model.assisted_trace, None
+            del model.assisted_trace
+            for i, name in enumerate(("draft", "verify", "accept")):
+                rec[f"round_ms_{name}"] = round(sum(r[i].elapsed_time(r[i + 1]) for r in ev) / len(ev), 3)
+            print(json.dumps(rec), flush=True)
+
+
 def batched_arms(model, n_req, B, text_len, reps, n1, n2, seed=0):
     """Wall ms of serving one request list: generate_batch / static batches of generate() / a B = 1 loop, and the scheduler's prediction."""
     import random
@@ -598,6 +670,7 @@ def main():
     ap.add_argument("--lookup", type=int, default=None, help="k: prompt-lookup decoding (as is / acceptance forced) against greedy; with --batched: the generate_batch arms")
     ap.add_argument("--constraint", action="store_true", help="greedy under a token automaton: plain / closed allow-list / open")
     ap.add_argument("--constraint-only", default=None, help="comma-separated B of the constraint arms (default 1,8)")
+    ap.add_argument("--constraint-draft", type=int, default=None, help="k: generate(constraint=, constraint_draft_tokens=k) against generate(constraint=)")
     ap.add_argument("--spec-kernel-only", type=int, default=None, help="k: lmod_spec_sample_bf16 alone, no model (for a kernel trace)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate.py measures on the GPU"
@@ -642,6 +715,9 @@ def main():
     if a.constraint:
         constraint_arms(model, [int(x) for x in a.constraint_only.split(",")] if a.constraint_only else [1, 8], a.text_len, a.reps,
                         a.n1, a.n2)
+    if a.constraint_draft:
+        constraint_draft_arms(model, a.constraint_draft, [int(x) for x in a.constraint_only.split(",")] if a.constraint_only else [1, 8],
+                              a.text_len, a.reps)
     if not a.sample:
         return
     arms = (True,) if a.device_arm_only else (True, False)
